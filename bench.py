@@ -1,7 +1,7 @@
 #!/usr/bin/env python3
 """Headline benchmark: SELFIES sequences/sec of the AR-CVAE training step on MI355X.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR]
   python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
          --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -18,6 +18,11 @@ global batch 2048 split over the N ranks -- and reports it as the `strong` objec
 One JSON line is printed by rank 0 with `roofline` (dominant kernel, live HIP-event timing) and
 `cpu_baseline` (the oracle = CPU restatement of the reference step, timed on this box's host
 cores; the MLX-CPU reference itself cannot run offline -- BASELINE.md section 2).
+
+`--dump-outputs DIR` writes what the last timed step of the headline leg computed as DIR/<name>.npy (outside the
+timed region).  Inputs and initial weights come from fixed seeds, so two builds run with the same arguments can be
+compared output for output -- within fp32 rounding: the order of some on-device sums varies from run to run, so two
+runs of one build agree closely (about 1e-5 after 25 steps of the default config), not bit for bit.
 """
 from __future__ import annotations
 
@@ -191,7 +196,14 @@ def parse_args(argv=None):
                          "and 128; N = 1, default config; 0 = skip)")
     ap.add_argument("--dry-launch", action="store_true",
                     help="print the torch.distributed.run command --gpus N would start, and exit (no GPU touched)")
-    return ap.parse_args(argv)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed (rank 0) as DIR/<name>.npy: the loss "
+                         "scalars, mu, logvar, z, the logits, every parameter's gradient and its post-Adam value (float32, "
+                         "at most 64 MB in all; see dump_outputs)")
+    args = ap.parse_args(argv)
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    return args
 
 
 def launch_ranks(args, argv) -> int:
@@ -244,6 +256,26 @@ def host_cores() -> int:
 
 def log(msg: str) -> None:
     print(f"[bench] {msg}", file=sys.stderr, flush=True)
+
+
+DUMP_BUDGET_BYTES = 64 * 10 ** 6
+NPY_HEADER_BYTES = 128
+
+
+def dump_outputs(path: str, named, budget: int = DUMP_BUDGET_BYTES) -> None:
+    """Write `named` (name -> host float array) as path/<name>.npy.  If the files would take more than `budget` bytes, every
+    array above a size cap is replaced by a fixed sample of `cap` of its elements (flattened, ascending positions drawn from
+    RandomState(0): the same positions on every run) written as path/<name>_sample.npy; the cap halves until the set fits."""
+    os.makedirs(path, exist_ok=True)
+    cap = max(a.size for a in named.values())
+    while sum(min(a.size, cap) * a.itemsize + NPY_HEADER_BYTES for a in named.values()) > budget:
+        cap //= 2
+    for name, a in named.items():
+        if a.size > cap:
+            idx = np.sort(np.random.RandomState(0).choice(a.size, cap, replace=False))
+            np.save(os.path.join(path, name + "_sample.npy"), a.reshape(-1)[idx])
+        else:
+            np.save(os.path.join(path, name + ".npy"), a)
 
 
 def cpu_baseline(sample_steps: int):
@@ -512,6 +544,17 @@ def main(argv=None):
     log("timing")
     dt, host_enq = timed(one_step, args.warmup, args.steps)
     scal = ws.scalars.cpu().numpy()
+    if args.dump_outputs and rank == 0:
+        # what a caller of the step receives from the last timed step, before any later probe runs on these buffers
+        named = {k: np.asarray(scal[i], dtype=np.float32) for i, k in enumerate(E.SCALAR_KEYS)}
+        named.update(mu=ws.mu.cpu().numpy(), logvar=ws.logvar.cpu().numpy(), z=ws.z.cpu().numpy(),
+                     logits=eng.gather_logits(ws).cpu().numpy())
+        for mod, st in (("encoder", enc), ("decoder", dec)):
+            for n in st.names():
+                named[f"grad.{mod}.{n}"] = st.g(n).cpu().numpy()
+                named[f"param.{mod}.{n}"] = st.p(n).cpu().numpy()
+        dump_outputs(args.dump_outputs, named)
+        log(f"outputs of the last timed step -> {args.dump_outputs}")
     comm = comm_probe(dp, one_step, total) if use_dp else None
     # a device-side gate or a persistent sweep that gave up waiting would mean the streams lost their order: no number
     # then -- and every rank leaves together (a lone exit would park the others in a barrier)

@@ -7,6 +7,8 @@ import os
 import subprocess
 import sys
 
+import pytest
+
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 
 
@@ -71,3 +73,57 @@ def test_bench_source_names_the_contract_fields():
               '"roofline"', '"cpu_baseline"', '"workload"', '"strong"', '"n_ranks_seen"', '"step_tflops_executed"',
               '"tick_model"', '"limiter"', '"bf16_mode"', '"other_configs"'):
         assert k in src, k
+
+
+def test_steps_below_one_is_refused():
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "0", "--dry-launch"], capture_output=True,
+                       text=True, timeout=120)
+    assert r.returncode != 0 and "--steps" in r.stderr
+
+
+def test_dump_outputs_keeps_to_its_budget_with_a_fixed_sample(tmp_path):
+    """Arrays that fit are written whole; past the budget the largest ones become fixed samples (same positions every run)."""
+    import numpy as np
+    sys.path.insert(0, ROOT)
+    import bench
+    rs = np.random.RandomState(5)
+    named = {"small": rs.rand(10).astype(np.float32), "scalar": np.asarray(np.float32(2.5)),
+             "big": rs.rand(600, 1000).astype(np.float32), "mid": rs.rand(100, 1000).astype(np.float64)}
+    bench.dump_outputs(str(tmp_path / "whole"), named)
+    for k, a in named.items():
+        assert np.array_equal(np.load(tmp_path / "whole" / f"{k}.npy"), a), k
+    budget = 10 ** 6
+    for run in ("a", "b"):
+        bench.dump_outputs(str(tmp_path / run), named, budget=budget)
+    files = sorted(os.listdir(tmp_path / "a"))
+    assert files == sorted(os.listdir(tmp_path / "b"))
+    assert sum(os.path.getsize(tmp_path / "a" / f) for f in files) <= budget
+    assert "small.npy" in files and "scalar.npy" in files and "big_sample.npy" in files
+    for f in files:
+        assert np.array_equal(np.load(tmp_path / "a" / f), np.load(tmp_path / "b" / f)), f
+    s = np.load(tmp_path / "a" / "big_sample.npy")
+    assert s.ndim == 1 and 0 < s.size < named["big"].size and np.isin(s, named["big"]).all()
+
+
+@pytest.mark.gpu
+def test_dump_outputs_is_the_last_timed_step(tmp_path):
+    """--dump-outputs on the headline leg: the loss it writes is the line's, every parameter has its gradient and its post-Adam
+    value, all float32 and finite, within 64 MB."""
+    import numpy as np
+    d = tmp_path / "out"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--steps", "3", "--warmup", "2", "--cpu-steps", "0",
+                        "--no-roofline", "--strong-global-batch", "0", "--bf16-steps", "0", "--configs2-steps", "0",
+                        "--sampler-reps", "0", "--dump-outputs", str(d)], capture_output=True, text=True, timeout=300)
+    assert r.returncode == 0, r.stderr[-2000:]
+    line = json.loads(r.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 3 and line["ms_per_step"] > 0
+    arrs = {f[:-4]: np.load(d / f) for f in os.listdir(d)}
+    assert sum(os.path.getsize(d / f) for f in os.listdir(d)) <= 64 * 10 ** 6
+    assert all(a.dtype == np.float32 and np.isfinite(a).all() for a in arrs.values())
+    assert float(arrs["total_loss"]) == line["elbo"]["total"] and float(arrs["recon_loss"]) == line["elbo"]["recon"]
+    assert arrs["logits"].shape == (64, 128, 80) and arrs["mu"].shape == arrs["z"].shape == (64, 128)
+    sys.path.insert(0, os.path.join(ROOT, "mlx-vae_amd"))
+    from arcvae_hip.store import decoder_shapes, encoder_shapes
+    for mod, shapes in (("encoder", encoder_shapes(80, 128, 256, 128, 1, 2)), ("decoder", decoder_shapes(80, 128, 256, 128, 1, 2))):
+        for n, shp in shapes.items():
+            assert arrs[f"grad.{mod}.{n}"].shape == arrs[f"param.{mod}.{n}"].shape == tuple(shp), (mod, n)
