@@ -347,6 +347,25 @@ int arcvae_dec_sample_chain(const int32_t* nxt, int32_t* tokens, int32_t* first_
  * uniform numbers from a counter-based generator keyed by (seed, row, step): the same seed and batch give the same molecules.  dense_logits [B*V, V] as written by arcvae_dec_forward_dense (mode 0); vocab_size <= 256; first_end as above. */
 int arcvae_dec_sample_chain_categorical(const float* dense_logits, int32_t* tokens, int32_t* first_end, int B, int V, int max_len,
                                         int end_token, float temperature, unsigned long long seed, arcvae_stream_t stream);
+/* EXTENSION (no reference counterpart: the reference decodes greedily) -- beam search and sequence log-likelihood over the dense
+ * logits [B*V, V] of arcvae_dec_forward_dense (mode 0), vocab_size <= 256.  Step term, fp32 without contraction:
+ * lp(c, v) = fl(x[b*V+c, v] * (1.0f / temperature)) - lse[b*V+c], a candidate's score fl(s + lp).
+ * arcvae_dec_row_lse: lse[r] = logsumexp(dense_logits[r, :] / temperature) of the R dense rows.
+ * arcvae_dec_beam_search: per batch row, width 1 <= K <= 32, from the start token 0; a live hypothesis proposes every token
+ * (end_token excluded while t < min_len), a finished one its pad_token continuation at the same score; the K best are kept under
+ * (score desc, parent slot asc, token asc).  Outputs tokens [B, K, max_len] (pad_token after the first end_token), scores [B, K]
+ * descending, lengths [B, K] (first end_token index + 1, max_len without one, 0 for an empty slot: score -inf, pad tokens).
+ * ws: caller-owned device scratch of at least arcvae_dec_beam_ws_bytes(B, K, max_len) bytes (pre-pass lists and back-pointers);
+ * 0 <= pad_token <= 255, 0 <= min_len <= max_len.
+ * arcvae_dec_sequence_logprob: out[b] = sum_{t<=e} lp(fed_t, x[b,t]) in order, fed_0 = 0, fed_t = x[b,t-1], e = the first t with
+ * x[b,t] == end_token (T-1 without one); tokens outside [0, V) are clamped. */
+int arcvae_dec_row_lse(const float* dense_logits, float* lse, long R, int V, float temperature, arcvae_stream_t stream);
+int arcvae_dec_beam_ws_bytes(int B, int K, int max_len, long* bytes);
+int arcvae_dec_beam_search(const float* dense_logits, const float* lse, int32_t* tokens, float* scores, int32_t* lengths, void* ws,
+                           long ws_bytes, int B, int V, int K, int max_len, int min_len, int end_token, int pad_token,
+                           float temperature, arcvae_stream_t stream);
+int arcvae_dec_sequence_logprob(const float* dense_logits, const float* lse, const int32_t* tokens, float* out, int B, int T, int V,
+                                int end_token, float temperature, arcvae_stream_t stream);
 /* Backward of arcvae_dec_forward_dense: embedding.weight, lstm_layer_l.{Wx,bias}, fc_out.{weight,bias}.
  * ws: dh [2,B*V,H], dG [B*V,4H], dtableD [V,4H], wcpart [V,4H,max(C,1)]. */
 int arcvae_dec_backward_dense(const float* emb, const float* const* Wx, const float* const* bias,

@@ -84,6 +84,10 @@ SIGNATURES = {
     "arcvae_dec_gather_logits": [_vp, _vp, _vp, _i, _i, _i, _vp],
     "arcvae_dec_sample_chain": [_vp, _vp, _vp, _i, _i, _i, _i, _vp],
     "arcvae_dec_sample_chain_categorical": [_vp, _vp, _vp, _i, _i, _i, _i, _f, C.c_ulonglong, _vp],
+    "arcvae_dec_row_lse": [_vp, _vp, _l, _i, _f, _vp],
+    "arcvae_dec_beam_ws_bytes": [_i, _i, _i, _lp],
+    "arcvae_dec_beam_search": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "arcvae_dec_sequence_logprob": [_vp, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     "arcvae_dec_backward_dense": [_vp, _pp, _pp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _pp, _pp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "arcvae_reparameterize": [_vp, _vp, _vp, _vp, _l, _vp],

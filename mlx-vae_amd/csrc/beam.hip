@@ -1,0 +1,408 @@
+// Beam search and sequence log-likelihood over the dense decoder table -- an EXTENSION with no reference behaviour to match
+// (the reference's sampler is the greedy walk, models/decoder_sampling.py:48-128).
+//
+// The decoder is stateless per step, so the next-token distribution depends only on (batch row, previous token):
+// logp[b, c, :] = log_softmax(dense_logits[b*V + c, :] / T), and the dense pass (arcvae_dec_forward_dense, mode 0) holds every
+// distribution a hypothesis can meet.  The step term is, in fp32 with no contraction,
+//     lp(c, v) = fl(x[b*V+c, v] * inv_temp) - lse_T[b*V+c],      a candidate's score = fl(s + lp).
+// Scores are chains of single IEEE operations in a fixed order, so the walk and the sequence log-likelihood agree bit for bit
+// with an fp32 restatement that performs the same operations (tests/beam_ref.py).
+//
+// Kernels (the sequence log-likelihood kernel is at the end of the file):
+//   row_lse    one wave per table row: lse_T = logsumexp(x * inv_temp).
+//   prepass    one wave per table row: the row's best K+1 children by (lp desc, token asc), the position of end_token among them,
+//              and the largest lp strictly below the last stored one (the "next" value).  A parent's best children are the same
+//              at every step, so they are found once: a step then merges K parents x K children, not K x V.
+//   walk       one wave per batch row: K rounds of a K-way merge of the parents' sorted child lists, back-pointers
+//              (parent slot, token) per step, backtracking at the end.
+//
+// Exactness of the pre-pass.  fl(s + .) is monotone, so a parent's children in (lp desc, token asc) order are also in (score desc,
+// token asc) order -- unless two children with different lp round to the same score.  The walk checks exactly that for the
+// children it uses: adjacent used children with equal scores and different lp, the spare stored child against the last used one,
+// and fl(s + next) against the last used one (a child beyond the stored list could tie with it and carry a smaller token).  A
+// parent that fails the check takes its children from a full scan of its row, ordered by (score desc, token asc) directly: the
+// result is the total order of the contract in every case, the scan being the rare path.
+#include "common.h"
+
+namespace {
+
+constexpr int BEAM_MAX_K = 32;
+constexpr int BEAM_MAX_V = 256;
+constexpr int BEAM_KP = BEAM_MAX_K + 1;      // stored children per row at most (K + 1)
+constexpr int BEAM_CHUNK = 6;               // stored children per lane and load batch of the walk's gather
+
+// The (score, token) that comes first under (score desc, token asc).
+__device__ __forceinline__ bool beam_before(float sa, int ta, float sb, int tb) {
+    return sa > sb || (sa == sb && ta < tb);
+}
+
+__device__ __forceinline__ void wave_best(float& s, int& t) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const float os = __shfl_xor(s, o, 64);
+        const int ot = __shfl_xor(t, o, 64);
+        if (beam_before(os, ot, s, t)) { s = os; t = ot; }
+    }
+}
+
+// Wave-wide: the M first entries of one row under (sc desc, token asc), sc[e] held by lane for token 4*lane+e, `ok[e]` marking
+// eligible entries.  Round i returns the best entry strictly after the one returned by round i-1; emit(i, sc, token) is called
+// with wave-uniform values.  Returns the number of entries emitted (M, or fewer when the row runs out); (*ps, *pt) = last one.
+template <typename Emit>
+__device__ __forceinline__ int wave_select(const float (&sc)[4], const bool (&ok)[4], int lane, int M, float* ps, int* pt,
+                                           Emit emit) {
+    float prev_s = INFINITY;
+    int prev_t = -1, n = 0;
+    for (int i = 0; i < M; ++i) {
+        float bs = -INFINITY;
+        int bt = 0x7fffffff;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int j = 4 * lane + e;
+            const bool after = sc[e] < prev_s || (sc[e] == prev_s && j > prev_t);
+            if (ok[e] && after && beam_before(sc[e], j, bs, bt)) { bs = sc[e]; bt = j; }
+        }
+        wave_best(bs, bt);
+        if (bt == 0x7fffffff) break;                      // nothing eligible left (wave-uniform)
+        emit(i, bs, bt);
+        prev_s = bs;
+        prev_t = bt;
+        ++n;
+    }
+    *ps = prev_s;
+    *pt = prev_t;
+    return n;
+}
+
+__device__ __forceinline__ void load_lp(const float* __restrict__ row, float l, float inv_temp, int V, int lane, float (&lp)[4],
+                                        bool (&ok)[4]) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int j = 4 * lane + e;
+        ok[e] = j < V;
+        const float a = ok[e] ? row[j] * inv_temp : 0.f;
+        lp[e] = ok[e] ? a - l : -INFINITY;
+    }
+}
+
+// ---- lse_T of every dense row (one wave per row) ------------------------------------------------------------------------
+__global__ __launch_bounds__(256) void beam_row_lse_kernel(const float* __restrict__ logits, float* lse, long R, int V,
+                                                           float inv_temp) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;
+    const float* x = logits + r * V;
+    float m = -INFINITY;
+    for (int w = lane; w < V; w += 64) m = fmaxf(m, x[w] * inv_temp);
+    m = wave_max(m);
+    float s = 0.f;
+    for (int w = lane; w < V; w += 64) s += expf(x[w] * inv_temp - m);
+    s = wave_sum(s);
+    if (lane == 0) lse[r] = m + logf(s);
+}
+
+// ---- pre-pass: per dense row the best M = min(K+1, V) children, end_token's position among them (255: absent) and the
+// largest lp strictly below the last stored one (-inf: none) ----------------------------------------------------------------
+__global__ __launch_bounds__(256) void beam_prepass_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
+                                                           float* LP, uint8_t* TK, uint8_t* EP, float* NX, long R, int V,
+                                                           int Kp, int end_token, float inv_temp) {
+    const int lane = threadIdx.x & 63;
+    const long r = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;                                   // wave-uniform
+    float lp[4];
+    bool ok[4];
+    load_lp(logits + r * V, lse[r], inv_temp, V, lane, lp, ok);
+    const int M = min(Kp, V);
+    int eos_at = 255;
+    float last_s;
+    int last_t;
+    wave_select(lp, ok, lane, M, &last_s, &last_t, [&](int i, float s, int t) {
+        if (lane == 0) {
+            LP[r * Kp + i] = s;
+            TK[r * Kp + i] = (uint8_t)t;
+        }
+        if (t == end_token) eos_at = i;
+    });
+    float nx = -INFINITY;
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        if (ok[e] && lp[e] < last_s) nx = fmaxf(nx, lp[e]);
+    nx = wave_max(nx);
+    if (lane == 0) {
+        EP[r] = (uint8_t)eos_at;
+        NX[r] = nx;
+    }
+}
+
+// The walk's rare path: parent score s, its row's first K children under (fl(s + lp) desc, token asc), `skip` excluded, into
+// cs/ct; returns how many.  Kept out of line: the common path should not carry its registers.
+__device__ __attribute__((noinline)) int beam_scan_row(const float* row, float l, float s, float inv_temp, int V, int K, int skip,
+                                                        int lane, float* cs, int* ct) {
+    float lp[4], sc[4];
+    bool ok[4];
+    load_lp(row, l, inv_temp, V, lane, lp, ok);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        sc[e] = s + lp[e];
+        if (4 * lane + e == skip) ok[e] = false;
+    }
+    float ls;
+    int lt;
+    return wave_select(sc, ok, lane, K, &ls, &lt, [&](int i, float sv, int tv) {
+        if (lane == 0) {
+            cs[i] = sv;
+            ct[i] = tv;
+        }
+    });
+}
+
+// ---- the walk: one wave per batch row ------------------------------------------------------------------------------------
+// Slot state (LDS): score ps (-inf = empty), last token pc, finished pf.  Step t: every parent's usable children go to
+// cs/ct/cl[p][0..cn[p]) sorted by (score desc, token asc) (plus the spare stored child at [K] when there is one); K merge
+// rounds pick the K best heads under (score desc, parent slot asc); bp[b, t, j] = parent | token << 8.
+__global__ __launch_bounds__(64) void beam_walk_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
+                                                       const float* __restrict__ LP, const uint8_t* __restrict__ TK,
+                                                       const uint8_t* __restrict__ EP, const float* __restrict__ NX,
+                                                       uint16_t* bp, int32_t* tokens, float* scores, int32_t* lengths,
+                                                       int V, int K, int max_len, int min_len, int end_token, int pad_token,
+                                                       float inv_temp) {
+    __shared__ float ps[BEAM_MAX_K], ns[BEAM_MAX_K];
+    __shared__ int pc[BEAM_MAX_K], pf[BEAM_MAX_K], nc[BEAM_MAX_K], nf[BEAM_MAX_K], np_[BEAM_MAX_K];
+    __shared__ float cs[BEAM_MAX_K][BEAM_KP], cl[BEAM_MAX_K][BEAM_KP];
+    __shared__ int ct[BEAM_MAX_K][BEAM_KP];
+    __shared__ int cn[BEAM_MAX_K], spare[BEAM_MAX_K], risky[BEAM_MAX_K];
+    __shared__ float nxt[BEAM_MAX_K];
+    __shared__ int cx[BEAM_MAX_K];
+    const int lane = threadIdx.x, b = blockIdx.x;
+    const int Kp = K + 1, nst = min(Kp, V);              // stored children per row
+    const long row0 = (long)b * V;
+    const float* LPb = LP + row0 * Kp;                    // this batch row's pre-pass lists
+    const uint8_t* TKb = TK + row0 * Kp;
+    const uint8_t* EPb = EP + row0;
+    const float* NXb = NX + row0;
+    if (lane < K) {
+        ps[lane] = lane == 0 ? 0.f : -INFINITY;
+        pc[lane] = 0;                                     // start token 0, as the greedy walk
+        pf[lane] = 0;
+    }
+    __syncthreads();
+    int t_end = max_len;
+    for (int t = 0; t < max_len; ++t) {
+        const bool no_eos = t < min_len;
+        // 1. each parent's children from the pre-pass lists: own parent's row data first, then the children in chunks whose
+        //    loads are all issued before their first use
+        if (lane < K) {
+            const float s = ps[lane];
+            risky[lane] = 0;
+            spare[lane] = 0;
+            cx[lane] = 255;
+            if (!(s > -INFINITY)) {
+                cn[lane] = 0;
+            } else if (pf[lane]) {                       // EOS is absorbing: one continuation, pad, same score
+                cn[lane] = 1;
+                cs[lane][0] = s;
+                cl[lane][0] = 0.f;
+                ct[lane][0] = pad_token;
+            } else {
+                const int c = pc[lane];
+                const int excl = no_eos ? EPb[c] : 255;
+                const int avail = nst - (excl < nst ? 1 : 0);
+                cx[lane] = excl;
+                nxt[lane] = NXb[c];
+                cn[lane] = min(K, avail);
+                spare[lane] = avail > K;
+            }
+        }
+        __syncthreads();
+        for (int e0 = 0; e0 < K * Kp; e0 += 64 * BEAM_CHUNK) {
+            float lv[BEAM_CHUNK];
+            int tv[BEAM_CHUNK];
+#pragma unroll
+            for (int k = 0; k < BEAM_CHUNK; ++k) {
+                const int e = e0 + lane + 64 * k, p = e / Kp, i = e - p * Kp;
+                tv[k] = -1;
+                if (e < K * Kp && i < nst && ps[p] > -INFINITY && !pf[p] && i != cx[p]) {
+                    const int o = pc[p] * Kp + i;
+                    lv[k] = LPb[o];
+                    tv[k] = TKb[o];
+                }
+            }
+#pragma unroll
+            for (int k = 0; k < BEAM_CHUNK; ++k) {
+                if (tv[k] < 0) continue;
+                const int e = e0 + lane + 64 * k, p = e / Kp, i = e - p * Kp;
+                const int j = i - (cx[p] < i ? 1 : 0);    // j <= K (the spare)
+                cl[p][j] = lv[k];
+                cs[p][j] = ps[p] + lv[k];
+                ct[p][j] = tv[k];
+            }
+        }
+        __syncthreads();
+        // 2. the order check (see the file comment)
+        for (int e = lane; e < K * K; e += 64) {
+            const int p = e / K, j = e - p * K;
+            if (pf[p] || j >= cn[p]) continue;
+            if (j + 1 < cn[p] || spare[p]) {
+                if (cs[p][j] == cs[p][j + 1] && cl[p][j] != cl[p][j + 1]) risky[p] = 1;
+            }
+            if (j == cn[p] - 1 && V > nst && ps[p] + nxt[p] == cs[p][j]) risky[p] = 1;
+        }
+        __syncthreads();
+        // 3. rare path: a full scan of the row of every parent that failed the check
+        unsigned long long rmask = __ballot(lane < K && risky[lane]);
+        while (rmask) {
+            const int p = __builtin_ctzll(rmask);
+            rmask &= rmask - 1;
+            const long row = row0 + pc[p];
+            const int n = beam_scan_row(logits + row * V, lse[row], ps[p], inv_temp, V, K, no_eos ? end_token : -1, lane,
+                                        cs[p], ct[p]);
+            if (lane == 0) cn[p] = n;
+            __syncthreads();
+        }
+        // 4. K-way merge of the sorted child lists: K rounds, best head under (score desc, parent slot asc)
+        int h = 0;
+        float head = (lane < K && cn[lane] > 0) ? cs[lane][0] : -INFINITY;
+        int filled = 0;
+        for (int r = 0; r < K; ++r) {
+            float bs = head;
+            int bl = head > -INFINITY ? lane : 0x7fffffff;
+            wave_best(bs, bl);
+            if (bl == 0x7fffffff) break;                  // no finite candidate left (wave-uniform)
+            if (lane == bl) {
+                const int tok = ct[lane][h];
+                ns[r] = bs;
+                nc[r] = tok;
+                nf[r] = pf[lane] || tok == end_token;
+                np_[r] = lane;
+                ++h;
+                head = h < cn[lane] ? cs[lane][h] : -INFINITY;
+            }
+            ++filled;
+        }
+        __syncthreads();
+        bool open = false;
+        if (lane < K) {
+            if (lane >= filled) {                         // empty slot
+                ns[lane] = -INFINITY;
+                nc[lane] = pad_token;
+                nf[lane] = 0;
+                np_[lane] = 255;
+            }
+            ps[lane] = ns[lane];
+            pc[lane] = nc[lane];
+            pf[lane] = nf[lane];
+            bp[((long)b * max_len + t) * K + lane] = (uint16_t)((np_[lane] & 255) | ((nc[lane] & 255) << 8));
+            open = ns[lane] > -INFINITY && !nf[lane];
+        }
+        __syncthreads();
+        // every hypothesis finished (or empty): the remaining steps would copy each slot onto itself with a pad token
+        if (__ballot(open) == 0ull) {
+            t_end = t + 1;
+            break;
+        }
+    }
+    // 5. backtrack
+    if (lane < K) {
+        const float s = ps[lane];
+        int32_t* out = tokens + ((long)b * K + lane) * max_len;
+        scores[(long)b * K + lane] = s;
+        for (int t = t_end; t < max_len; ++t) out[t] = pad_token;
+        if (!(s > -INFINITY)) {
+            for (int t = 0; t < t_end; ++t) out[t] = pad_token;
+            lengths[(long)b * K + lane] = 0;
+        } else {
+            int slot = lane, fe = max_len;
+            for (int t = t_end - 1; t >= 0; --t) {
+                const uint16_t v = bp[((long)b * max_len + t) * K + slot];
+                const int tok = v >> 8;
+                out[t] = tok;
+                if (tok == end_token) fe = t;
+                slot = min((int)(v & 255), K - 1);
+            }
+            lengths[(long)b * K + lane] = fe < max_len ? fe + 1 : max_len;
+        }
+    }
+}
+
+// ---- sequence log-likelihood: one wave per row, sum_{t<=e} lp(fed_t, x_t) in order, e = first end_token (T-1 if none) --------
+__global__ __launch_bounds__(256) void beam_seq_logprob_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
+                                                               const int32_t* __restrict__ x, float* out, int B, int T, int V,
+                                                               int end_token, float inv_temp) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;                                   // wave-uniform
+    const int32_t* xr = x + (long)b * T;
+    float s = 0.f;
+    bool done = false;
+    for (int t0 = 0; t0 < T && !done; t0 += 64) {
+        const int t = t0 + lane;
+        float lp = 0.f;
+        bool is_end = false;
+        if (t < T) {
+            const int v = min(max(xr[t], 0), V - 1);
+            const int c = t == 0 ? 0 : min(max(xr[t - 1], 0), V - 1);
+            const long row = (long)b * V + c;
+            const float a = logits[row * V + v] * inv_temp;
+            lp = a - lse[row];
+            is_end = v == end_token;
+        }
+        const unsigned long long ends = __ballot(is_end);
+        const int n = ends ? __builtin_ctzll(ends) + 1 : min(64, T - t0);
+        for (int i = 0; i < n; ++i) s = s + __shfl(lp, i, 64);   // left to right, as the walk accumulates
+        done = ends != 0ull;
+    }
+    if (lane == 0) out[b] = s;
+}
+
+long beam_ws_bytes(int B, int K, int max_len) {
+    const long rows = (long)B * BEAM_MAX_V, Kp = K + 1;
+    return rows * Kp * 4 + rows * 4 + (long)B * max_len * K * 2 + rows * Kp + rows;
+}
+
+}  // namespace
+
+extern "C" int arcvae_dec_row_lse(const float* dense_logits, float* lse, long R, int V, float temperature, hipStream_t stream) {
+    if (!dense_logits || !lse || R <= 0 || V <= 0 || V > BEAM_MAX_V || !(temperature > 0.f)) return ARCVAE_ERR_ARG;
+    hipLaunchKernelGGL(beam_row_lse_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, stream, dense_logits, lse, R, V,
+                       1.0f / temperature);
+    return arcvae_launch_status();
+}
+
+extern "C" int arcvae_dec_beam_ws_bytes(int B, int K, int max_len, long* bytes) {
+    if (!bytes || B <= 0 || K < 1 || K > BEAM_MAX_K || max_len <= 0) return ARCVAE_ERR_ARG;
+    *bytes = beam_ws_bytes(B, K, max_len);
+    return ARCVAE_OK;
+}
+
+// ws layout: LP [B*256, K+1] f32 | NX [B*256] f32 | bp [B, max_len, K] u16 | TK [B*256, K+1] u8 | EP [B*256] u8
+// (the pre-pass rows are sized for the largest vocabulary, 256, so that the size depends on (B, K, max_len) alone)
+extern "C" int arcvae_dec_beam_search(const float* dense_logits, const float* lse, int32_t* tokens, float* scores,
+                                      int32_t* lengths, void* ws, long ws_bytes, int B, int V, int K, int max_len, int min_len,
+                                      int end_token, int pad_token, float temperature, hipStream_t stream) {
+    if (!dense_logits || !lse || !tokens || !scores || !lengths || !ws) return ARCVAE_ERR_ARG;
+    if (B <= 0 || V <= 0 || V > BEAM_MAX_V || K < 1 || K > BEAM_MAX_K || max_len <= 0 || min_len < 0 || min_len > max_len)
+        return ARCVAE_ERR_ARG;
+    if (pad_token < 0 || pad_token > 255 || !(temperature > 0.f)) return ARCVAE_ERR_ARG;   // bp keeps a token in 8 bits
+    if (ws_bytes < beam_ws_bytes(B, K, max_len)) return ARCVAE_ERR_ARG;
+    const long rows = (long)B * BEAM_MAX_V, Kp = K + 1, R = (long)B * V;
+    char* w = (char*)ws;
+    float* LP = (float*)w;
+    float* NX = LP + rows * Kp;
+    uint16_t* bp = (uint16_t*)(NX + rows);
+    uint8_t* TK = (uint8_t*)(bp + (long)B * max_len * K);
+    uint8_t* EP = TK + rows * Kp;
+    const float inv_temp = 1.0f / temperature;
+    hipLaunchKernelGGL(beam_prepass_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, stream, dense_logits, lse, LP, TK, EP, NX,
+                       R, V, (int)Kp, end_token, inv_temp);
+    hipLaunchKernelGGL(beam_walk_kernel, dim3(B), dim3(64), 0, stream, dense_logits, lse, LP, TK, EP, NX, bp, tokens, scores,
+                       lengths, V, K, max_len, min_len, end_token, pad_token, inv_temp);
+    return arcvae_launch_status();
+}
+
+extern "C" int arcvae_dec_sequence_logprob(const float* dense_logits, const float* lse, const int32_t* tokens, float* out, int B,
+                                           int T, int V, int end_token, float temperature, hipStream_t stream) {
+    if (!dense_logits || !lse || !tokens || !out || B <= 0 || T <= 0 || V <= 0 || V > BEAM_MAX_V || !(temperature > 0.f))
+        return ARCVAE_ERR_ARG;
+    hipLaunchKernelGGL(beam_seq_logprob_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, stream, dense_logits, lse, tokens, out, B, T,
+                       V, end_token, 1.0f / temperature);
+    return arcvae_launch_status();
+}

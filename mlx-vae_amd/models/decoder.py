@@ -83,3 +83,31 @@ class MLXAutoregressiveDecoder(HipModule):
         out = torch.empty(B, T, self.vocab_size, dtype=torch.float32, device=dev)
         call("arcvae_dec_gather_logits", ptr(ws.logits), ptr(ws.fed), ptr(out), B, T, self.vocab_size, stream_ptr())
         return out
+
+    def sequence_log_prob(self, target_seq, conditions, temperature: float = 1.0) -> torch.Tensor:
+        """Extension (absent in the reference): [B] float32 log-likelihood of each row of target_seq [B, T] under `conditions`,
+        sum over t <= e of log_softmax(logits(fed_t) / temperature)[x_t], fed_0 = 0 (the start token), fed_t = x_{t-1}, e the
+        first end_token (T-1 without one).  One dense pass (B*V rows) + arcvae_dec_row_lse + arcvae_dec_sequence_logprob: the
+        scores generate_beam returns are this value of the tokens it returns, bit for bit."""
+        if not temperature > 0.0:
+            raise ValueError("temperature must be > 0")
+        dev = self.store.device
+        cond = as_f32(conditions, dev)
+        tgt = as_tokens(target_seq, dev)
+        if tgt.dim() != 2 or tgt.shape[1] < 1:
+            raise ValueError("target_seq must be [B, T] with T >= 1")
+        B, T = tgt.shape
+        if cond.numel() != B * self.num_conditions:
+            raise ValueError("conditions must be [B, num_conditions]")
+        if bool(((tgt < 0) | (tgt >= self.vocab_size)).any()):
+            raise ValueError(f"target_seq tokens must lie in [0, {self.vocab_size})")
+        ws = self.workspace(B, T)
+        ws.cond.copy_(cond.reshape(B, self.num_conditions))
+        E.decoder_forward_dense(self.store, ws, self.dims, mode=0, keep_gpre=False, alone=True)
+        lse = torch.empty(B * self.vocab_size, dtype=torch.float32, device=dev)
+        out = torch.empty(B, dtype=torch.float32, device=dev)
+        call("arcvae_dec_row_lse", ptr(ws.logits), ptr(lse), B * self.vocab_size, self.vocab_size, float(temperature),
+             stream_ptr())
+        call("arcvae_dec_sequence_logprob", ptr(ws.logits), ptr(lse), ptr(tgt), ptr(out), B, T, self.vocab_size,
+             self.end_token, float(temperature), stream_ptr())
+        return out

@@ -5,7 +5,8 @@ sampling" is argmax(softmax(logits / T)) = greedy; tokens after EOS are still ge
 early stopping the output is cut where every row has emitted EOS.  One dense decoder pass
 (B*V rows) + one table walk replaces the reference's max_length dependent steps and its per-step
 host sync; `load_from_decoder` is an explicit extension to sample from trained weights, and `sample=True` the true categorical
-sampling the reference marks TODO (decoder_sampling.py:115-116): an extension with no reference behaviour to match."""
+sampling the reference marks TODO (decoder_sampling.py:115-116): an extension with no reference behaviour to match.  So is
+`generate_beam` (beam search with scores, csrc/beam.hip); `decoder.sequence_log_prob` scores given sequences."""
 from __future__ import annotations
 
 import torch
@@ -101,3 +102,43 @@ class MLXAutoregressiveDecoderSampling:
         if early_stopping:
             tokens = tokens[:, :min(int(first_end.max().item()) + 1, max_length)]
         return tokens.clone()
+
+    def generate_beam(self, z, conditions, max_length: int = 80, beam_width: int = 4, temperature: float = 1.0,
+                      min_length: int = 0, early_stopping: bool = True):
+        """Extension (absent in the reference): the beam_width most probable sequences per row under log_softmax(logits / T),
+        found by beam search -> (tokens [B, K, L] int32, scores [B, K] float32, descending).  z is accepted and unused (Q2).
+        Positions after a hypothesis' first end_token hold pad_token; end_token is not proposed before step min_length; ties
+        are broken by parent slot, then token (the lower first).  A slot with no finite candidate (beam_width above what the
+        vocabulary can fill) has score -inf and pad tokens.  early_stopping: L = the longest returned hypothesis (first EOS + 1,
+        max_length without one); otherwise L = max_length.  Each score equals decoder.sequence_log_prob of its tokens."""
+        import ctypes as C
+        dec = self.decoder
+        V = dec.vocab_size
+        if not temperature > 0.0:
+            raise ValueError("temperature must be > 0")
+        if not 1 <= int(beam_width) <= 32:
+            raise ValueError("beam_width must lie in [1, 32]")
+        if int(max_length) < 1 or not 0 <= int(min_length) <= int(max_length):
+            raise ValueError("need max_length >= 1 and 0 <= min_length <= max_length")
+        if V > 256 or not 0 <= self.pad_token <= 255:
+            raise ValueError("beam search needs vocab_size <= 256 and 0 <= pad_token <= 255")
+        K, T = int(beam_width), int(max_length)
+        dev = dec.store.device
+        cond = as_f32(conditions, dev)
+        B = cond.shape[0]
+        ws = dec.workspace(B, T)
+        ws.cond.copy_(cond.reshape(B, dec.num_conditions))
+        nbytes = C.c_long(0)
+        call("arcvae_dec_beam_ws_bytes", B, K, T, C.byref(nbytes))
+        scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        lse = torch.empty(B * V, dtype=torch.float32, device=dev)
+        tokens = torch.empty(B, K, T, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+        lengths = torch.empty(B, K, dtype=torch.int32, device=dev)
+        E.decoder_forward_dense(dec.store, ws, dec.dims, mode=0, keep_gpre=False, alone=True)
+        call("arcvae_dec_row_lse", ptr(ws.logits), ptr(lse), B * V, V, float(temperature), stream_ptr())
+        call("arcvae_dec_beam_search", ptr(ws.logits), ptr(lse), ptr(tokens), ptr(scores), ptr(lengths), ptr(scratch),
+             nbytes.value, B, V, K, T, int(min_length), self.end_token, self.pad_token, float(temperature), stream_ptr())
+        if early_stopping:
+            tokens = tokens[:, :, :int(lengths.max().item())].contiguous()
+        return tokens, scores

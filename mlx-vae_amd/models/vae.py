@@ -32,11 +32,21 @@ class ARCVAE:
         return logits, mu, logvar, z
 
     def generate(self, batch_size: int, conditions, max_length: int = 80, temperature: float = 1.0, *, sample: bool = False,
-                 seed: int = 0) -> torch.Tensor:
+                 seed: int = 0, beam_width: Optional[int] = None) -> torch.Tensor:
         """models/vae.py:101-131: z ~ N(0,I) (unused downstream, Q2) -> greedy sampler.  sample / seed (keyword-only extension):
-        true categorical sampling instead of the reference's argmax, see MLXAutoregressiveDecoderSampling."""
+        true categorical sampling instead of the reference's argmax, see MLXAutoregressiveDecoderSampling.  beam_width
+        (keyword-only extension): the best hypothesis of a beam search of that width, [B, L] (generate_beam, early stopping)."""
         dev = self.decoder_sampling.decoder.store.device
         z = torch.randn(batch_size, self.latent_dim, device=dev)
+        if beam_width is not None:
+            if sample:
+                raise ValueError("beam_width and sample=True are exclusive")
+            tokens, _ = self.decoder_sampling.generate_beam(z, conditions, max_length=max_length, beam_width=beam_width,
+                                                            temperature=temperature)
+            best = tokens[:, 0, :]
+            ended = best == self.decoder_sampling.end_token          # cut where every row's best hypothesis has ended
+            length = torch.where(ended.any(1), ended.int().argmax(1) + 1, best.shape[1])
+            return best[:, :int(length.max().item())].contiguous()
         return self.decoder_sampling.generate_with_temperature(z, conditions, max_length=max_length,
                                                                temperature=temperature, sample=sample, seed=seed)
 
