@@ -1594,6 +1594,255 @@ __device__ __forceinline__ void ps_take_role(unsigned* cnt, unsigned* cucnt, uns
     }
 }
 
+// Layer-split form (LS = 1; H 256, L 2, at most 8 rows per XCD, fp32 4x4x1 blocks): the XCD's two layers as TWO recurrence
+// chains with a flag line each ([layer][xcc][32]: layer 0 at sync + PS_FLAGS, layer 1 at sync + PS_LS_FLAGS), one block of
+// 512 threads per CU.  Waves 0-3 run the layer-0 chain (Wh0 h0_{t-1} -> reduce -> epilogue -> h0_t -> flag), waves 4-7 the
+// layer-1 chain (Wh1 h1_{t-1} -> ... -> h1_t -> flag); each layer's four waves hold the K quarters of its Wh slice in
+// registers (64 VGPRs).  The cross-layer product Wx1 h0_t is on neither chain: the layer-0 waves compute it at their tick
+// t+1 from the h0_t operands they have just loaded, with the Wx1 slice in LDS, into a ring of RD slots that holds each
+// quarter's four unreduced accumulators; the layer-1 wave of the same quarter starts its Wh1 chain from them -- the same
+// instructions in the same order as the one-chain form, so the results are bit-identical to it.  Layer 0 runs ahead of
+// layer 1, at most RD slots.  No block-wide barrier inside the tick loops: within a layer, the wave that polls the flag
+// line tells the other three through an LDS word; the partial sums and the ring slots are handed over through LDS words a
+// wave sets after its LDS writes (release); only the epilogue wave of a layer stores exchanged h, drains its stores and
+// then publishes its flag (the one-lane flag row of the hand-off table: sc1 poll, the other waves load behind the LDS word
+// the polling wave sets).  A wave that gives up clears s_ok and raises PS_ERR; every spin checks both and is bounded.
+constexpr int PS_LS_FLAGS = 1024;   // layer-1 flag lines of the layer-split forward ([8 XCDs][32]; the two-group form's words:
+                                    // never used by the same shape), inside what arcvae_enc_prologue re-arms
+constexpr int PS_LS_RD = 2;         // ring slots of Wx1 h0 accumulators (16 KB each)
+constexpr size_t PS_LS_LDS = sizeof(float) * (8192 + 2 * 1024 + PS_LS_RD * 4096) + 64 * sizeof(unsigned);
+
+__device__ __forceinline__ unsigned ls_ld(const unsigned* w) { return __hip_atomic_load(w, __ATOMIC_ACQUIRE, __HIP_MEMORY_SCOPE_WORKGROUP); }
+__device__ __forceinline__ void ls_st(unsigned* w, unsigned v) { __hip_atomic_store(w, v, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP); }
+
+__device__ void lstm_fwd_persist_split(const PersistArgs& a) {
+    constexpr int H = 256, G = 4 * H, CW = 32, UW = 8, CHW = 4, RD = PS_LS_RD;
+    extern __shared__ __attribute__((aligned(16))) float lds[];
+    f32x4* wxl = reinterpret_cast<f32x4*>(lds);      // [quarter][chunk][4-group][32 lanes] the Wx1 slice (32 KB)
+    float* red = lds + 8192;                         // [layer][4 waves][8 rows][32 columns] reduced partials of a tick
+    f32x4* ring = reinterpret_cast<f32x4*>(lds + 8192 + 2 * 1024);   // [RD][quarter][4 accumulators][64 lanes]
+    unsigned* cw = reinterpret_cast<unsigned*>(lds + 8192 + 2 * 1024 + RD * 4096);
+    // cw[ly]: tick whose flags the layer's poll wave has seen; cw[2 + ly]: partial arrivals of the layer (4 per tick);
+    // cw[4 + q]: ring slots filled by layer-0 wave q; cw[8 + q]: ring slots consumed by layer-1 wave q
+    __shared__ unsigned s_role, s_xcc;
+    __shared__ int s_ok;
+    arcvae_set_prio(a.prio);
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ly = wave >> 2, kw = wave & 3;
+    const int B = a.B, T = a.T;
+    if (tid == 0) {
+        s_xcc = ps_xcc_id();
+        unsigned g_, r_;
+        ps_take_role<1>(a.cnt, a.cucnt, s_xcc, g_, r_);
+        s_role = r_;
+        s_ok = 1;
+        if (blockIdx.x == 0 && a.start_signal)
+            __hip_atomic_fetch_add(a.start_signal, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    }
+    if (tid < 16) cw[tid] = 0;
+    __syncthreads();
+    const unsigned xcc = __builtin_amdgcn_readfirstlane(s_xcc), role = __builtin_amdgcn_readfirstlane(s_role);
+    if (xcc >= 8 || role >= 32) {
+        if (tid == 0) atomicAdd(a.sync + PS_ERR, 1u);
+        return;
+    }
+    const int RX = a.RX, row0 = xcc * RX;
+    auto wsrc = [&](int si, int kc, int rp, int ko) -> const float* {
+        return a.W[si] + (long)(((rp >> 2) & 3) * H + (rp >> 4) * 4 + (rp & 3)) * H + 16 * kc + ko;
+    };
+    const int rg = lane >> 5, cg = (lane >> 2) & 7, ij = lane & 3;
+    f32x4 wq[CHW][4];                                // Wh_ly: W[k..k+3][4cg + ij] of my quarter
+#pragma unroll
+    for (int c = 0; c < CHW; ++c)
+#pragma unroll
+        for (int g4 = 0; g4 < 4; ++g4)
+            wq[c][g4] = *reinterpret_cast<const f32x4*>(wsrc(ly, kw * CHW + c, role * CW + 4 * cg + ij, 4 * g4));
+    for (int i = tid; i < 4 * CHW * 4 * 32; i += 512) {   // Wx1 (a.W[2]) -> LDS, in the order its waves read it
+        const int l32 = i & 31, g4 = (i >> 5) & 3, kc = i >> 7;
+        wxl[i] = *reinterpret_cast<const f32x4*>(wsrc(2, kc, role * CW + 4 * (l32 >> 2) + (l32 & 3), 4 * g4));
+    }
+    __syncthreads();
+    const int mrow = min(row0 + max(min(4 * rg + ij, RX - 1), 0), B - 1);
+    const unsigned qoff = (unsigned)(((long)mrow * H + 64 * kw + 4 * cg) * 4);
+    const long sH = (long)B * H, sG = (long)B * G, lH = (long)T * sH, lG = (long)T * sG;
+    const unsigned* xflags = a.sync + (ly == 0 ? PS_FLAGS : PS_LS_FLAGS) + xcc * 32;
+    unsigned* my_flag = a.sync + (ly == 0 ? PS_FLAGS : PS_LS_FLAGS) + xcc * 32 + role;
+    // epilogue (wave 0 of the layer): lane = (row, unit) pair
+    const int erow = lane >> 3, ul = lane & 7, eb = row0 + erow, unit = role * UW + ul;
+    const bool eact = kw == 0 && erow < RX && eb < B;
+    const bool tr = a.trace && xcc == 0 && role == 0 && kw == 0 && lane == 0;
+#ifdef ARCVAE_PS_STAMPS   // diagnostic build: four stamps per tick and chain at trace[8 t + 4 ly + k]
+#define LS_STAMP(k) do { if (tr) a.trace[8 * (long)t + 4 * ly + (k)] = wall_clock64(); } while (0)
+#else
+#define LS_STAMP(k) do { } while (0)
+#endif
+    // a wait on an LDS word set by another wave of the block (bounded; false: the block gives up)
+    auto lds_wait = [&](const unsigned* w, unsigned target) -> bool {
+        unsigned spins = 0;
+        while ((int)(ls_ld(w) - target) < 0) {
+            if (!__hip_atomic_load(&s_ok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP) || ++spins > 4000000u) {
+                if (lane == 0) { atomicAdd(a.sync + PS_ERR, 1u); __hip_atomic_store(&s_ok, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+                return false;
+            }
+            __builtin_amdgcn_s_sleep(1);
+        }
+        return true;
+    };
+    // every CU of my XCD has published tick t-1 of my layer: wave 1 of the layer polls the line, the others wait on cw[ly]
+    auto flags_seen = [&](int t) -> bool {
+        if (kw == 1) {
+            unsigned spins = 0;
+            while (true) {
+                const unsigned v = (lane < 32) ? __hip_atomic_load(xflags + lane, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) : (unsigned)t;
+                if (__all((int)(v - (unsigned)t) >= 0)) break;
+                if (++spins > 4000000u || __hip_atomic_load(a.sync + PS_ERR, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)
+                    || !__hip_atomic_load(&s_ok, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP)) {
+                    if (lane == 0) { atomicAdd(a.sync + PS_ERR, 1u); __hip_atomic_store(&s_ok, 0, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP); }
+                    return false;
+                }
+                __builtin_amdgcn_s_sleep(1);
+            }
+            if (lane == 0) ls_st(cw + ly, (unsigned)t);
+            return true;
+        }
+        return lds_wait(cw + ly, (unsigned)t);
+    };
+    // the rank-1 updates of one source (A operand Q: my row's 4 consecutive k, block cg holding k = 64 kw + 32 m + 4 cg + e)
+#define LS_Q1(Q, W_, M_, AB_)                                                                                                \
+    { const f32x4 w_ = W_(2 * M_ + (AB_ >> 2), AB_ & 3);                                                                   \
+      acc[0] = __builtin_amdgcn_mfma_f32_4x4x1f32(Q[M_].x, w_.x, acc[0], 3, AB_, 0);                                      \
+      acc[1] = __builtin_amdgcn_mfma_f32_4x4x1f32(Q[M_].y, w_.y, acc[1], 3, AB_, 0);                                      \
+      acc[2] = __builtin_amdgcn_mfma_f32_4x4x1f32(Q[M_].z, w_.z, acc[2], 3, AB_, 0);                                      \
+      acc[3] = __builtin_amdgcn_mfma_f32_4x4x1f32(Q[M_].w, w_.w, acc[3], 3, AB_, 0); }
+#define LS_Q8(Q, W_, M_) LS_Q1(Q, W_, M_, 0) LS_Q1(Q, W_, M_, 1) LS_Q1(Q, W_, M_, 2) LS_Q1(Q, W_, M_, 3) \
+                         LS_Q1(Q, W_, M_, 4) LS_Q1(Q, W_, M_, 5) LS_Q1(Q, W_, M_, 6) LS_Q1(Q, W_, M_, 7)
+#define LS_WREG(C_, G_) wq[C_][G_]
+#define LS_WLDS(C_, G_) wxl[((kw * CHW + (C_)) * 4 + (G_)) * 32 + (lane & 31)]
+    // the epilogue of my layer's tick t (wave 0 of the layer): gates from the four waves' partials, c in a register
+    float cst = 0.f;
+    auto epilogue = [&](int t, const float (&pv)[4]) {
+        if (eact) {
+            const int cb = erow * CW + 16 * (ul >> 2) + (ul & 3);
+            const float* rl = red + ly * 1024;
+            float v[4];
+#pragma unroll
+            for (int g = 0; g < 4; ++g) {
+                const int o = cb + 4 * g;
+                v[g] = (rl[o] + rl[256 + o]) + (rl[512 + o] + rl[768 + o]);
+            }
+            const float gi = chain_sigmoid(v[0] + pv[0]);
+            const float gf = chain_sigmoid(v[1] + pv[1]);
+            const float gg = chain_tanh(v[2] + pv[2]);
+            const float go = chain_sigmoid(v[3] + pv[3]);
+            const float c = t > 0 ? gf * cst + gi * gg : gi * gg;   // MLX: cell=None at t == 0 -> c = i*g
+            cst = c;
+            const long hb = (long)eb * H + unit;
+            const float hval = go * chain_tanh(c);
+            a.hseq[ly * lH + (long)t * sH + hb] = hval;
+            if (a.comb && ly == 1 && t == T - 1) a.comb[(long)eb * 2 * H + unit] = hval;
+            float* gp = a.gseq + ly * lG + (long)t * sG + (long)eb * G + unit;
+            gp[0] = gi; gp[H] = gf; gp[2 * H] = gg; gp[3 * H] = go;
+            a.cseq[ly * lH + (long)t * sH + hb] = c;
+        }
+        ps_stores_in_l2();                                       // my h stores have reached the XCD's L2
+        if (lane == 0) __hip_atomic_store(my_flag, (unsigned)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+    // my quarter's partial of the tick -> red, then count it (the LDS writes complete before the release)
+    auto put_partial = [&](const f32x4 (&acc)[4]) {
+        float* rp = red + ly * 1024 + kw * 256 + (4 * rg) * CW + 4 * cg + ij;
+#pragma unroll
+        for (int i = 0; i < 4; ++i) rp[i * CW] = (acc[0][i] + acc[1][i]) + (acc[2][i] + acc[3][i]);
+        if (lane == 0) __hip_atomic_fetch_add(cw + 2 + ly, 1u, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_WORKGROUP);
+    };
+
+    if (ly == 0) {
+        for (int t = 0; t <= T; ++t) {                   // tick T: only Wx1 h0_{T-1}
+            LS_STAMP(0);
+            float pv[4] = {0.f, 0.f, 0.f, 0.f};
+            if (eact && t < T) {                         // token -> table0 row: requested before the wait
+                int tk = a.x_tb[(long)t * B + eb];
+                tk = min(max(tk, 0), a.V - 1);
+                const float* pre = a.table0 + (long)tk * G;
+                pv[0] = pre[unit]; pv[1] = pre[H + unit]; pv[2] = pre[2 * H + unit]; pv[3] = pre[3 * H + unit];
+            }
+#ifndef ARCVAE_PS_STAMPS
+            if (tr && t < T) a.trace[2 * t] = wall_clock64();
+#endif
+            if (t > 0 && !flags_seen(t)) return;
+            LS_STAMP(1);
+            f32x4 qh[2];
+            if (t > 0) {
+                const __amdgpu_buffer_rsrc_t rs = ps_rsrc(a.hseq + (long)(t - 1) * sH, sH * 4);
+                qh[0] = ps_load_sc1_x4(rs, qoff);
+                qh[1] = ps_load_sc1_x4(rs, qoff + 128);
+            }
+            if (t < T) {
+                f32x4 acc[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+                if (t > 0) { LS_Q8(qh, LS_WREG, 0) LS_Q8(qh, LS_WREG, 1) }
+                put_partial(acc);
+                if (kw == 0) {
+                    if (!lds_wait(cw + 2, 4u * (unsigned)(t + 1))) return;
+                    LS_STAMP(2);
+                    epilogue(t, pv);
+                    LS_STAMP(3);
+#ifndef ARCVAE_PS_STAMPS
+                    if (tr && t == 0) a.trace[1] = wall_clock64();
+#endif
+                }
+            }
+            if (t > 0) {                                 // off the chain: Wx1 h0_{t-1} -> ring slot (t-1) % RD
+                const int j = t - 1;
+                if (j >= RD && !lds_wait(cw + 8 + kw, (unsigned)(j - RD + 1))) return;
+                f32x4 acc[4];
+#pragma unroll
+                for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
+                LS_Q8(qh, LS_WLDS, 0) LS_Q8(qh, LS_WLDS, 1)
+                f32x4* rs = ring + ((j % RD) * 4 + kw) * 256 + lane;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) rs[64 * e] = acc[e];
+                if (lane == 0) ls_st(cw + 4 + kw, (unsigned)(j + 1));
+            }
+        }
+    } else {
+        float pv[4] = {0.f, 0.f, 0.f, 0.f};
+        if (eact) { const float* pre = a.bias[1]; pv[0] = pre[unit]; pv[1] = pre[H + unit]; pv[2] = pre[2 * H + unit]; pv[3] = pre[3 * H + unit]; }
+        for (int t = 0; t < T; ++t) {
+            LS_STAMP(0);
+            if (t > 0 && !flags_seen(t)) return;
+            LS_STAMP(1);
+            f32x4 qh[2];
+            if (t > 0) {
+                const __amdgpu_buffer_rsrc_t rs = ps_rsrc(a.hseq + lH + (long)(t - 1) * sH, sH * 4);
+                qh[0] = ps_load_sc1_x4(rs, qoff);
+                qh[1] = ps_load_sc1_x4(rs, qoff + 128);
+            }
+            if (!lds_wait(cw + 4 + kw, (unsigned)(t + 1))) return;   // ring slot t: my quarter's Wx1 h0_t accumulators
+            f32x4 acc[4];
+            const f32x4* rs = ring + ((t % RD) * 4 + kw) * 256 + lane;
+#pragma unroll
+            for (int e = 0; e < 4; ++e) acc[e] = rs[64 * e];
+            if (t > 0) { LS_Q8(qh, LS_WREG, 0) LS_Q8(qh, LS_WREG, 1) }
+            put_partial(acc);                            // (its release also orders the ring reads before the next store)
+            if (lane == 0) ls_st(cw + 8 + kw, (unsigned)(t + 1));
+            if (kw == 0) {
+                if (!lds_wait(cw + 3, 4u * (unsigned)(t + 1))) return;
+                LS_STAMP(2);
+                epilogue(t, pv);
+                LS_STAMP(3);
+#ifndef ARCVAE_PS_STAMPS
+                if (tr) a.trace[2 * (t + 1) + 1] = wall_clock64();
+#endif
+            }
+        }
+    }
+#undef LS_WLDS
+#undef LS_WREG
+#undef LS_Q8
+#undef LS_Q1
+#undef LS_STAMP
+}
+
 // MF = 1 (H = 256, at most 8 rows per XCD, L <= 2): the contraction on v_mfma_f32_4x4x1 blocks instead of 16x16x4 tiles.
 // With 8 rows a 16-row tile is half empty: 96 instructions of 32 cycles per wave and tick, 1.28 us of the tick, for
 // half that much useful work.  Blocks = 2 row groups x 8 column groups: ONE 4x4x1 instruction (8 cycles) is the rank-1
@@ -1604,10 +1853,15 @@ __device__ __forceinline__ void ps_take_role(unsigned* cnt, unsigned* cucnt, uns
 // NG = 2: the two-group form -- 512 blocks, two per CU (the register budget of launch bounds (256, 2) and an LDS floor that
 // admits exactly two), every XCD's rows as two independent recurrences of up to 16 rows with their own flag lines
 // (ps_take_role); a block is the RT = 1 kernel on its group's rows.
-template <int NT, int LL, int RT, int MF = 0, int NG = 1>   // RT = 16-row MFMA tiles per XCD (rows per XCD RX <= 16 * RT)
-__global__ __launch_bounds__(256, NG) void lstm_fwd_persist_kernel(PersistArgs a) {
+// LS = 1: the layer-split form (lstm_fwd_persist_split above; 512 threads).
+template <int NT, int LL, int RT, int MF = 0, int NG = 1, int LS = 0>   // RT = 16-row MFMA tiles per XCD (rows per XCD RX <= 16 * RT)
+__global__ __launch_bounds__(256 * (1 + LS), NG) void lstm_fwd_persist_kernel(PersistArgs a) {
     static_assert(MF == 0 || (NT == 2 && RT == 1 && LL <= 2), "4x4x1 form: H = 256, one row tile, L <= 2");
     static_assert(NG == 1 || (RT == 1 && MF == 0), "two groups: one 16-row tile per group");
+    static_assert(LS == 0 || (NT == 2 && LL == 2 && RT == 1 && MF == 1 && NG == 1), "layer split: H 256, L 2, fp32 4x4x1 form");
+    if constexpr (LS != 0) {
+        lstm_fwd_persist_split(a);
+    } else {
     // MF = 2 (throughput mode, ARCVAE_PERSIST_BF16): the same blocks on v_mfma_f32_4x4x4_16b_bf16 -- a lane's four consecutive
     // k (one 16-byte load of h, one float4 of its weight column) are ONE instruction instead of four: 48 instead of 192
     // matrix instructions per wave and tick, weights in 96 instead of 192 VGPRs (packed bf16), h and the weights rounded
@@ -1940,14 +2194,15 @@ __global__ __launch_bounds__(256, NG) void lstm_fwd_persist_kernel(PersistArgs a
         if (tid == 0) __hip_atomic_store(my_flag, (unsigned)(s + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
         PS_STAMP_END();
     }
+    }
 }
 
-template <int NT, int LL, int RT, int MF = 0, int NG = 1>
+template <int NT, int LL, int RT, int MF = 0, int NG = 1, int LS = 0>
 void launch_persist(const PersistArgs& a, size_t lds, hipStream_t s) {
     // > 64 KB of dynamic LDS has to be allowed per kernel; set on every call (idempotent, no host state kept)
-    (void)hipFuncSetAttribute((const void*)lstm_fwd_persist_kernel<NT, LL, RT, MF, NG>,
+    (void)hipFuncSetAttribute((const void*)lstm_fwd_persist_kernel<NT, LL, RT, MF, NG, LS>,
                               hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
-    hipLaunchKernelGGL((lstm_fwd_persist_kernel<NT, LL, RT, MF, NG>), dim3(256 * NG), dim3(256), lds, s, a);
+    hipLaunchKernelGGL((lstm_fwd_persist_kernel<NT, LL, RT, MF, NG, LS>), dim3(256 * NG), dim3(256 * (1 + LS)), lds, s, a);
 }
 // LDS allocation of a two-group block (ARCVAE_PERSIST2_LDS_KB, default 56): more than a third of a CU's 160 KB and at most
 // half of it, so that a CU admits exactly two of them
@@ -1962,6 +2217,12 @@ inline bool persist_two_groups(int B, int H, int L, int which /* 1 forward sweep
     return (arcvae_env_int("ARCVAE_PERSIST2", 1) & which) != 0 && H == 256 && L >= 1 && L <= 2 && ceil_div(B, 8) > 16 && ceil_div(B, 8) <= 32;
 }
 inline int persist_row_tiles(int B) { return ceil_div(B, 8) > 16 ? 2 : 1; }
+// Layer-split forward (lstm_fwd_persist_split): fp32, H 256, L 2, at most 8 rows per XCD, 4x4x1 blocks.  ARCVAE_LAYER_SPLIT=0
+// (read at every call) keeps the one-chain form.
+inline bool persist_layer_split(int B, int H, int L) {
+    return arcvae_env_int("ARCVAE_LAYER_SPLIT", 1) != 0 && arcvae_env_int("ARCVAE_FWD_MFMA", 1) != 0 && H == 256 && L == 2
+           && ceil_div(B, 8) <= 8;
+}
 // LDS allocation floor of the register-stationary persistent kernels (ARCVAE_PERSIST_LDS_KB, default 81 = more than half
 // of a CU's 160 KB): two of their blocks can then never share a CU, whatever else is resident.
 inline size_t persist_lds_floor() { return (size_t)arcvae_env_int("ARCVAE_PERSIST_LDS_KB", 81) * 1024; }
@@ -3053,6 +3314,10 @@ extern "C" int arcvae_enc_lstm_forward_persistent(const int32_t* x_tb, const flo
     if (!(flags & 1)) {   // bit 0: sync_ws was re-armed by arcvae_enc_prologue
         rc = arcvae_zero(reinterpret_cast<float*>(sync_ws), 1, PS_WORDS, PS_WORDS, stream);
         if (rc != ARCVAE_OK) return rc;
+        if (!(flags & ARCVAE_PERSIST_BF16) && persist_layer_split(B, H, L)) {   // the layer-1 flag lines
+            rc = arcvae_zero(reinterpret_cast<float*>(sync_ws + PS_LS_FLAGS), 1, 256, 256, stream);
+            if (rc != ARCVAE_OK) return rc;
+        }
     }
     PersistArgs a;
     a.x_tb = x_tb; a.table0 = table0; a.hseq = hseq; a.cseq = cseq; a.gseq = gseq; a.comb = comb;
@@ -3083,6 +3348,8 @@ extern "C" int arcvae_enc_lstm_forward_persistent(const int32_t* x_tb, const flo
     if (NT == 2 && L <= 2 && a.RX <= 8 && arcvae_env_int("ARCVAE_FWD_MFMA", 1) != 0) {
         if (flags & ARCVAE_PERSIST_BF16) {   // throughput mode: the 4x4x4 bf16 form of the same blocks
             if (L == 1) launch_persist<2, 1, 1, 2>(a, lds, stream); else launch_persist<2, 2, 1, 2>(a, lds, stream);
+        } else if (persist_layer_split(B, H, L)) {
+            launch_persist<2, 2, 1, 1, 1, 1>(a, lds > PS_LS_LDS ? lds : PS_LS_LDS, stream);
         } else {
             if (L == 1) launch_persist<2, 1, 1, 1>(a, lds, stream); else launch_persist<2, 2, 1, 1>(a, lds, stream);
         }
