@@ -413,6 +413,32 @@ int arcvae_adam_update_finalize(float* params, const float* grads, float* m, flo
                                 double beta2, double eps, const unsigned* guard_a, const unsigned* guard_b,
                                 const float* rowloss, int B, float* stats, float* scalars, int Z, int T, arcvae_stream_t stream);
 
+/* ---- property predictor head (an extension: the reference's branch cannot run) ------------------------
+ * Extends complete_vae_loss.py:64-74 (`property_predictor(z)` + losses/prop.py:5-40 `property_prediction_loss`, with the
+ * arity fixed) and trainer.py:75-76 (a third Adam, over the predictor).  Predictor: pred = fc2(tanh(fc1(z))),
+ * W1 [Hp,Z], b1 [Hp], W2 [C,Hp], b2 [C]; prop_loss = mean over B*C of (pred - cond)^2 -> scalars[5], lambda_prop * prop_loss
+ * -> scalars[6] (lambda_prop = hyper[5]).  1 <= Z <= 512, 1 <= C <= 8, 1 <= Hp <= 256, else ARCVAE_ERR_ARG.
+ * ws: the per-row partials (B * (2 Hp + C + 1) floats, arcvae_prop_ws_floats); every call states its capacity in ws_floats
+ * and an undersized one is ARCVAE_ERR_ARG. */
+int arcvae_prop_ws_floats(int B, int Z, int C, int Hp, long* floats);
+/* Forward only (PropertyPredictor.__call__, the loss forward): pred [B,C] (may be null when scalars is given) and, when
+ * scalars is non-null, the two loss scalars (cond and hyper required).  Two launches when the loss is asked for. */
+int arcvae_prop_forward(const float* z, const float* cond, const float* W1, const float* b1, const float* W2,
+                        const float* b2, const float* hyper, float* pred, float* scalars, float* ws, long ws_floats,
+                        int B, int Z, int C, int Hp, arcvae_stream_t stream);
+/* Training, ONE launch on the step's chain behind arcvae_latent_loss (which wrote d_mu_raw / d_lv_raw): forward, per-row
+ * dpred = lambda_prop * 2 (pred - cond) / (B C), and dz = d(lambda_prop * prop_loss)/dz folded INTO (+=) d_mu_raw / d_lv_raw
+ * through z = mu + eps exp(logvar/2), mu = 2 tanh(mu_raw/2), logvar = tanh(lv_raw/2) - 1.  Leaves the partials in ws;
+ * pred (optional) receives the predictions. */
+int arcvae_prop_backward(const float* z, const float* cond, const float* eps, const float* mu_raw, const float* lv_raw,
+                         const float* W1, const float* b1, const float* W2, const float* b2, const float* hyper,
+                         float* d_mu_raw, float* d_lv_raw, float* pred, float* ws, long ws_floats, int B, int Z, int C,
+                         int Hp, arcvae_stream_t stream);
+/* The predictor's weight gradients and loss scalars from the partials of arcvae_prop_backward: sums over rows in an order
+ * fixed by B alone (contiguous row slices, each in row order, added in slice order: bitwise repeatable).  The gradients are OVERWRITTEN ("="), unlike the rest of this ABI. */
+int arcvae_prop_wgrad(const float* z, const float* ws, long ws_floats, const float* hyper, float* dW1, float* db1,
+                      float* dW2, float* db2, float* scalars, int B, int Z, int C, int Hp, arcvae_stream_t stream);
+
 /* ---- small helpers ---------------------------------------------------------------------------------- */
 int arcvae_colsum_accum(const float* X, int rows, int cols, int ld, float* out, float scale,
                         arcvae_stream_t stream);

@@ -107,6 +107,10 @@ SIGNATURES = {
     "arcvae_gate_set": [_vp, C.c_uint, _i, _vp],
     "arcvae_tile_weights": [_pp, _pp, _ip, _ip, _i, _i, _vp],
     "arcvae_copy_buffers": [_pp, _pp, _lp, _i, _vp],
+    "arcvae_prop_ws_floats": [_i, _i, _i, _i, _lp],
+    "arcvae_prop_forward": [_vp] * 10 + [_l, _i, _i, _i, _i, _vp],
+    "arcvae_prop_backward": [_vp] * 14 + [_l, _i, _i, _i, _i, _vp],
+    "arcvae_prop_wgrad": [_vp, _vp, _l] + [_vp] * 6 + [_i, _i, _i, _i, _vp],
 }
 
 LONG_RESULTS = {"arcvae_enc_lstm_bwd_rs_part_floats"}      # size queries returning `long`; everything else returns an int code

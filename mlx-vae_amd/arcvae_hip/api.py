@@ -13,23 +13,33 @@ from .engine import SCALAR_KEYS, StepEngine
 _ENGINES: "weakref.WeakKeyDictionary" = weakref.WeakKeyDictionary()
 
 
-def engine_for(encoder, decoder) -> StepEngine:
-    """One StepEngine (workspaces, side stream, captured graphs) per (encoder, decoder) pair."""
+def engine_for(encoder, decoder, predictor=None) -> StepEngine:
+    """One StepEngine (workspaces, side stream, captured graphs) per (encoder, decoder, predictor): a step captured
+    without a predictor is never replayed with one, nor the reverse.  The key of the plain pair is id(decoder).
+    A predictor on a pair that runs data-parallel is refused (ValueError)."""
     per_enc = _ENGINES.setdefault(encoder, {})
-    key = id(decoder)
+    if predictor is not None and getattr(per_enc.get(id(decoder)), "dp", None) is not None:
+        from .dp import PREDICTOR_DP_UNSUPPORTED
+        raise ValueError(PREDICTOR_DP_UNSUPPORTED)
+    key = id(decoder) if predictor is None else (id(decoder), id(predictor))
     if key not in per_enc:
         if encoder.dims != decoder.dims:
             raise ValueError("encoder and decoder were built with different dimensions")
-        per_enc[key] = StepEngine(encoder.store, decoder.store, encoder.dims)
+        eng = StepEngine(encoder.store, decoder.store, encoder.dims,
+                         prop=predictor.store if predictor is not None else None)
+        eng.predictor = predictor      # held: its id stays this engine's key while the engine lives
+        per_enc[key] = eng
     return per_enc[key]
 
 
-def enable_data_parallel(encoder, decoder, group=None):
+def enable_data_parallel(encoder, decoder, group=None, predictor=None):
     """Route loss_forward / value_and_grad of this (encoder, decoder) pair through arcvae_hip.dp.EngineDataParallel: every
     call then takes the GLOBAL batch (identical on all ranks), works on this rank's rows and returns the global batch's
     loss scalars; mu / logvar / z in the result are the LOCAL rows'.  torch.distributed must be initialised (one process
     per GPU; backend nccl = RCCL).  Returns the driver (rank, world)."""
-    from .dp import EngineDataParallel
+    from .dp import PREDICTOR_DP_UNSUPPORTED, EngineDataParallel
+    if predictor is not None:
+        raise ValueError(PREDICTOR_DP_UNSUPPORTED)
     eng = engine_for(encoder, decoder)
     if getattr(eng, "dp", None) is None:
         eng.dp = EngineDataParallel(eng, group)
@@ -64,8 +74,10 @@ def _as_dict(eng: StepEngine, ws, clone: bool, status: bool = False) -> Dict[str
 
 
 def loss_forward(encoder, decoder, x, conditions, eps=None, coins=None, teacher_forcing_ratio: float = 0.9,
-                 **hyper) -> Dict[str, torch.Tensor]:
-    eng = engine_for(encoder, decoder)
+                 predictor=None, **hyper) -> Dict[str, torch.Tensor]:
+    """predictor (models.PropertyPredictor, optional): also prop_loss / weighted_prop_loss and "pred"; hyper must then
+    include lambda_prop (ValueError otherwise)."""
+    eng = engine_for(encoder, decoder, predictor)
     B, T = int(x.shape[0]), int(x.shape[1])
     if coins is None:
         coins = draw_coins(T, teacher_forcing_ratio)
@@ -76,14 +88,18 @@ def loss_forward(encoder, decoder, x, conditions, eps=None, coins=None, teacher_
         x, conditions = _dev_batch(eng, x, conditions)
         return _as_dict(eng, dp.forward_loss(x, conditions, _local_eps(dp, eps, B), coins, **hyper), clone=True)
     eng.forward_loss(x, conditions, eps, coins, **hyper)
-    return _as_dict(eng, eng.workspace(B, T, train=False), clone=True)
+    out = _as_dict(eng, eng.workspace(B, T, train=False), clone=True)
+    if predictor is not None:
+        out["pred"] = eng.workspace(B, T, train=False).pred.clone()
+    return out
 
 
 def value_and_grad(encoder, decoder, x, conditions, eps=None, coins=None, teacher_forcing_ratio: float = 0.9,
-                   lr: Optional[float] = None, **hyper):
+                   lr: Optional[float] = None, predictor=None, **hyper):
     """(loss dict, (encoder grad tree, decoder grad tree)); with `lr` given the two Adam updates are applied
-    in the same captured step (trainer.py:305-333)."""
-    eng = engine_for(encoder, decoder)
+    in the same captured step (trainer.py:305-333).  With a predictor (hyper must include lambda_prop, ValueError
+    otherwise): (loss dict, (encoder, decoder, predictor grad trees)) and three Adam updates."""
+    eng = engine_for(encoder, decoder, predictor)
     B, T = int(x.shape[0]), int(x.shape[1])
     if coins is None:
         coins = draw_coins(T, teacher_forcing_ratio)
@@ -98,6 +114,8 @@ def value_and_grad(encoder, decoder, x, conditions, eps=None, coins=None, teache
         return _as_dict(eng, ws, clone=False, status=True), (encoder.gradients(), decoder.gradients())
     eng.train_step(x, conditions, eps, coins, lr=lr if lr is not None else 0.0, update=lr is not None, **hyper)
     ws = eng.workspace(B, T, train=True)
+    if predictor is not None:
+        return _as_dict(eng, ws, clone=False, status=True), (encoder.gradients(), decoder.gradients(), predictor.gradients())
     return _as_dict(eng, ws, clone=False, status=True), (encoder.gradients(), decoder.gradients())
 
 

@@ -432,6 +432,12 @@ def shard_plan(n_rows: int, rank: int, world: int):
     return lo, hi, False
 
 
+# The predictor's gradient bucket and its global-row divisor under data parallelism are not built (a follow-up to the
+# property predictor head): refused, never run with a wrong divisor.
+PREDICTOR_DP_UNSUPPORTED = ("a property predictor cannot be combined with data parallelism yet (follow-up to the property "
+                            "predictor head: its gradient bucket and global-row divisor across ranks); train it single-process")
+
+
 class EngineDataParallel:
     """N ranks x row shard == one process x global batch for the two calls the trainer makes (reference trainer.py:242-333
     is single-process; this layer is defined by that equivalence).  Every rank holds the same weights, the same dataset
@@ -447,6 +453,8 @@ class EngineDataParallel:
     once and shared."""
 
     def __init__(self, engine, group: Optional[dist.ProcessGroup] = None):
+        if getattr(engine, "prop", None) is not None:
+            raise ValueError(PREDICTOR_DP_UNSUPPORTED)
         if not dist.is_initialized():
             raise RuntimeError("EngineDataParallel needs an initialised torch.distributed process group")
         self.eng, self.group = engine, group

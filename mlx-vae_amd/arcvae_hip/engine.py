@@ -377,6 +377,29 @@ def latent_loss(ws: Workspace, d: ModelDims, free_bits: float, with_grads: bool)
          ws.B, d.Z, ws.T, float(free_bits), stream_ptr())
 
 
+def prop_backward(prop: ParamStore, ws: Workspace, d: ModelDims, hp: int) -> None:
+    """The property predictor on the step's chain (csrc/prop.hip): forward, dpred, dz folded into d(mu_raw) / d(lv_raw).
+    Must follow latent_loss(..., True), which writes those two and zeroes scalars[5..6]."""
+    call("arcvae_prop_backward", ptr(ws.z), ptr(ws.cond), ptr(ws.eps), ptr(ws.mu_raw), ptr(ws.lv_raw),
+         ptr(prop.p("fc1.weight")), ptr(prop.p("fc1.bias")), ptr(prop.p("fc2.weight")), ptr(prop.p("fc2.bias")),
+         ptr(ws.hyper), ptr(ws.dmu_raw), ptr(ws.dlv_raw), ptr(ws.pred), ptr(ws.prop_ws), C.c_long(ws.prop_ws.numel()),
+         ws.B, d.Z, d.C, hp, stream_ptr())
+
+
+def prop_wgrad(prop: ParamStore, ws: Workspace, d: ModelDims, hp: int) -> None:
+    """The predictor's gradients (overwritten) and scalars[5..6]: fixed-order row sums of prop_backward's partials."""
+    call("arcvae_prop_wgrad", ptr(ws.z), ptr(ws.prop_ws), C.c_long(ws.prop_ws.numel()), ptr(ws.hyper),
+         ptr(prop.g("fc1.weight")), ptr(prop.g("fc1.bias")), ptr(prop.g("fc2.weight")), ptr(prop.g("fc2.bias")),
+         ptr(ws.scalars), ws.B, d.Z, d.C, hp, stream_ptr())
+
+
+def prop_forward(prop: ParamStore, ws: Workspace, d: ModelDims, hp: int) -> None:
+    """Forward-only predictor + scalars[5..6] (loss forward / validation): after latent_loss(..., False)."""
+    call("arcvae_prop_forward", ptr(ws.z), ptr(ws.cond), ptr(prop.p("fc1.weight")), ptr(prop.p("fc1.bias")),
+         ptr(prop.p("fc2.weight")), ptr(prop.p("fc2.bias")), ptr(ws.hyper), ptr(ws.pred), ptr(ws.scalars),
+         ptr(ws.prop_ws), C.c_long(ws.prop_ws.numel()), ws.B, d.Z, d.C, hp, stream_ptr())
+
+
 def _inline(key, fn, stream) -> None:
     with torch.cuda.stream(stream):
         fn()
@@ -902,10 +925,20 @@ class StepEngine:
               "eager" plain launches; "graph" the whole step as ONE forked hipGraph (kept for comparison).
     """
 
-    def __init__(self, enc: ParamStore, dec: ParamStore, dims: ModelDims, precision: Optional[str] = None):
+    def __init__(self, enc: ParamStore, dec: ParamStore, dims: ModelDims, precision: Optional[str] = None,
+                 prop: Optional[ParamStore] = None):
         dims.validate()
         _lib.load()  # fail loudly when the extension is missing
         self.enc, self.dec, self.d = enc, dec, dims
+        # property predictor (models/property_predictor.py, csrc/prop.hip): None = the plain step, launch for launch
+        self.prop = prop
+        self.prop_hidden = 0
+        if prop is not None:
+            hp, z = prop.shapes["fc1.weight"]
+            if z != dims.Z or tuple(prop.shapes["fc2.weight"]) != (dims.C, hp):
+                raise ValueError(f"property predictor shape {tuple(prop.shapes['fc2.weight'])} x {z} does not match the "
+                                 f"model (num_conditions {dims.C}, latent_dim {dims.Z})")
+            self.prop_hidden = int(hp)
         # "fp32" (default): the parity path (1e-4 against the oracle).  "bf16": throughput mode (SURVEY.md section 8(d)
         # Config 2, "bf16-in/fp32-acc") -- every matrix product off the latency-bound chain takes bf16 operands with f32
         # accumulation: the decoder's B*V-row GEMMs, the weight-gradient GEMMs, and the LSTM sweeps where they run on the
@@ -1053,6 +1086,11 @@ class StepEngine:
                     and (B > 128 or not bptt_reduce_scatter_ok(ws, self.d))):
                 ws.pl_h = torch.empty(self.d.L * T * B * self.d.H * 3 // 2, dtype=torch.float32, device=self.device)
                 ws.pl_g = torch.empty(self.d.L * T * B * 4 * self.d.H * 3 // 2, dtype=torch.float32, device=self.device)
+            if self.prop is not None:
+                n = C.c_long(0)
+                _lib.check(lib.arcvae_prop_ws_floats(B, self.d.Z, self.d.C, self.prop_hidden, C.byref(n)), "arcvae_prop_ws_floats")
+                ws.prop_ws = torch.empty(n.value, dtype=torch.float32, device=self.device)
+                ws.pred = torch.empty(B, self.d.C, dtype=torch.float32, device=self.device)
             self._ws[key] = ws
             self._probe_persistent(ws)
         return self._ws[key]
@@ -1075,12 +1113,16 @@ class StepEngine:
             ws.psync.zero_()
 
     def set_hyper(self, ws: Workspace, **kw) -> None:
+        if self.prop is not None and "lambda_prop" not in kw:
+            # never a value left over from an earlier call (or a silent 0: predictor gradients all zero)
+            raise ValueError("a step with a property predictor needs lambda_prop")
         h = dict(self.hyper_host)
         h.update(kw)
         self.hyper_host = h
-        vals = (h["beta"], h["lambda_collapse"], h["lambda_mi"], h["target_mi"], h["free_bits"])
+        vals = (h["beta"], h["lambda_collapse"], h["lambda_mi"], h["target_mi"], h["free_bits"],
+                float(h["lambda_prop"]) if self.prop is not None else 0.0)   # hyper[5]: with a predictor only
         if ws._hyper_vals != vals:  # epoch-scheduled values change rarely: skip the H2D copy otherwise
-            ws.hyper.copy_(torch.tensor(list(vals) + [0.0, 0.0, 0.0], dtype=torch.float32))
+            ws.hyper.copy_(torch.tensor(list(vals) + [0.0, 0.0], dtype=torch.float32))
             ws._hyper_vals = vals
 
     def load_inputs(self, ws: Workspace, x, cond, eps=None, coins=None) -> None:
@@ -1165,13 +1207,22 @@ class StepEngine:
         and gradients, then the encoder backward.  Does NOT wait for the decoder."""
         fb = float(self.hyper_host["free_bits"])
 
+        # With a predictor the fused seam's backward phase is never used (its dz has to reach d(mu_raw) / d(lv_raw) before
+        # the heads' dcomb chain, which the fused seam forms itself): the five-launch seam runs, on every path of the step.
+        fused_bwd = self.prop is None
+
         def prologue():
             if fuse_forward:
-                self._enc_fwd(ws, True, start_signal, seam=3)      # (fused seam: loss + dcomb chain in the same launch)
-            elif seam_fused_ok(ws, self.d):
+                # (fused seam: loss + dcomb chain in the same launch)
+                self._enc_fwd(ws, True, start_signal, seam=3 if fused_bwd else 1)
+            elif fused_bwd and seam_fused_ok(ws, self.d):
                 encoder_seam(self.enc, ws, self.d, fb, 2)          # data-parallel step: `stats` is global by now
+            if self.prop is not None and ws.seam_bwd_done:
+                raise _lib.ArcvaeHipError("internal: the fused seam's backward ran with a property predictor attached")
             if not ws.seam_bwd_done:
                 latent_loss(ws, self.d, fb, True)
+                if self.prop is not None:
+                    prop_backward(self.prop, ws, self.d, self.prop_hidden)
 
         # the tail chunk's token-table half goes to the SIDE stream: the decoder finished long ago and, unlike a
         # fourth stream, `side` owns a hardware queue of its own (HIP maps streams onto 4 queues), so the two
@@ -1201,6 +1252,9 @@ class StepEngine:
     def _finish_ops(self, ws: Workspace, lr: float, update: bool, with_recon: bool, dec_adam: bool, gates: Optional[Gates]):
         """The launches of a step's finish as a closure (its own segment, or the end of the main segment: _enqueue_step)."""
         def fin():
+            if self.prop is not None:
+                # the predictor's gradients and loss scalars: main is idle here while aux / side finish the step's tail
+                prop_wgrad(self.prop, ws, self.d, self.prop_hidden)
             if gates is not None:
                 gates.join()
             ga, gb = self.guards(ws)
@@ -1212,6 +1266,8 @@ class StepEngine:
                 call("arcvae_adam_update_finalize", ptr(st.flat), ptr(st.grad), ptr(st.adam_m), ptr(st.adam_v),
                      C.c_long(st.numel_padded), float(lr), 0.9, 0.999, 1e-8, ga, gb, ptr(ws.rowloss), ws.B, ptr(ws.stats),
                      ptr(ws.scalars), self.d.Z, ws.T, stream_ptr())
+                if self.prop is not None:
+                    adam_update(self.prop, lr, guards=(ga, gb))
                 return
             if with_recon:   # CE sum + recon/total scalars in one launch
                 call("arcvae_recon_finalize", ptr(ws.rowloss), ws.B, ptr(ws.stats), ptr(ws.scalars), self.d.Z, ws.T,
@@ -1222,6 +1278,8 @@ class StepEngine:
                 if dec_adam:
                     adam_update(self.dec, lr, guards=(ga, gb))
                 adam_update(self.enc, lr, guards=(ga, gb))
+                if self.prop is not None:
+                    adam_update(self.prop, lr, guards=(ga, gb))
         return fin
 
     def _enqueue_step(self, ws: Workspace, lr: float, global_rows: int, update: bool, run=_inline) -> None:
@@ -1288,6 +1346,8 @@ class StepEngine:
         self.enqueue_encoder_forward(ws, backward=False)
         self.enqueue_decoder(ws, B, backward=False, wait_current=False)
         latent_loss(ws, self.d, float(self.hyper_host["free_bits"]), False)
+        if self.prop is not None:
+            prop_forward(self.prop, ws, self.d, self.prop_hidden)
         self.enqueue_recon(ws)
         ga, gb = self.guards(ws)
         call("arcvae_loss_finalize", ptr(ws.stats), ptr(ws.scalars), self.d.Z, ws.T, ga, gb, stream_ptr())

@@ -15,14 +15,16 @@ def complete_vae_loss(encoder, decoder, property_predictor, x, conditions, beta:
                       eps: Optional[torch.Tensor] = None, coins: Optional[Sequence[bool]] = None) -> dict:
     """total = recon + beta*kl + collapse + lambda_prop*prop + mi_penalty  (complete_vae_loss.py:76-82).
 
-    `property_predictor` must be None: the reference's predictor branch cannot run (it calls
-    property_prediction_loss with the wrong arity), so prop_loss is identically 0.
+    `property_predictor`: None (prop_loss is then identically 0, as in the reference, whose predictor branch cannot
+    run) or a models.PropertyPredictor -- an extension: prop_loss = mean over B*C
+    of (predictor(z) - conditions)^2 on the sampled z.
     `eps` / `coins` are additive hooks to inject the reparameterisation noise and the per-step
     teacher-forcing decisions; by default they are drawn as the reference draws them."""
+    hyper = dict(beta=beta, lambda_collapse=lambda_collapse, lambda_mi=lambda_mi, target_mi=target_mi, free_bits=free_bits)
     if property_predictor is not None:
-        raise NotImplementedError("property_predictor is not supported (unreachable in the reference, Q10)")
+        hyper["lambda_prop"] = lambda_prop
     out = api.loss_forward(encoder, decoder, x, conditions, eps=eps, coins=coins,
-                           teacher_forcing_ratio=teacher_forcing_ratio, beta=beta, lambda_collapse=lambda_collapse,
-                           lambda_mi=lambda_mi, target_mi=target_mi, free_bits=free_bits)
-    # lambda_prop * 0 == 0: weighted_prop_loss stays the zero the kernel wrote
+                           teacher_forcing_ratio=teacher_forcing_ratio, predictor=property_predictor, **hyper)
+    out.pop("pred", None)
+    # without a predictor, lambda_prop * 0 == 0: weighted_prop_loss stays the zero the kernel wrote
     return out

@@ -3,5 +3,6 @@ from .encoder import MLXEncoder
 from .decoder import MLXAutoregressiveDecoder
 from .decoder_sampling import MLXAutoregressiveDecoderSampling
 from .vae import ARCVAE
+from .property_predictor import PropertyPredictor
 
-__all__ = ["MLXEncoder", "MLXAutoregressiveDecoder", "MLXAutoregressiveDecoderSampling", "ARCVAE"]
+__all__ = ["MLXEncoder", "MLXAutoregressiveDecoder", "MLXAutoregressiveDecoderSampling", "ARCVAE", "PropertyPredictor"]

@@ -68,6 +68,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dist_backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend (extension): nccl = RCCL over xGMI, one rank per GPU; gloo carries "
                          "device tensors through the host (several ranks on one GPU: tests)")
+    ap.add_argument("--property_predictor_hidden", type=int, default=0,
+                    help="hidden width of a property predictor on z trained with --lambda_prop (extension; 0 = no predictor, "
+                         "--lambda_prop is then unused as in the reference)")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default=None,
                     help="fp32: the parity path (default); bf16: throughput mode -- matrix products on bf16 operands with "
                          "f32 accumulation, parameters and optimizer state in f32 (extension; ARCVAE_PRECISION does the same)")
@@ -112,6 +115,9 @@ def main(argv=None):
     args = build_parser().parse_args(argv)
     if args.precision:                      # read when the step engine of the model is created (arcvae_hip/engine.py)
         os.environ["ARCVAE_PRECISION"] = args.precision
+    if args.property_predictor_hidden and (args.world_size or int(os.environ.get("WORLD_SIZE", "1"))) > 1:
+        from arcvae_hip.dp import PREDICTOR_DP_UNSUPPORTED
+        raise ValueError(PREDICTOR_DP_UNSUPPORTED)
     rank, world = init_data_parallel(args)
     import builtins
     print = builtins.print if rank == 0 else (lambda *a, **k: None)   # noqa: A001  N ranks run the same flow; rank 0 reports
@@ -182,8 +188,13 @@ def main(argv=None):
     if world > 1:
         from arcvae_hip import api
         api.enable_data_parallel(vae.encoder, vae.decoder)
+    predictor = None
+    if args.property_predictor_hidden:
+        from models.property_predictor import PropertyPredictor
+        predictor = PropertyPredictor(args.latent_dim, args.num_conditions, args.property_predictor_hidden, device=args.device)
+        print(f"  Property predictor: hidden={args.property_predictor_hidden}, lambda_prop={args.lambda_prop}")
     trainer = ARCVAETrainerWithLoss(
-        encoder=vae.encoder, decoder=vae.decoder, property_predictor=None, dataset=train_dataset,
+        encoder=vae.encoder, decoder=vae.decoder, property_predictor=predictor, dataset=train_dataset,
         batch_size=args.batch_size, learning_rate=args.learning_rate, beta_start=args.beta_start,
         beta_end=args.beta_end, beta_warmup_epochs=args.beta_warmup_epochs, lambda_prop=args.lambda_prop,
         lambda_collapse=args.lambda_collapse, free_bits=args.free_bits, lambda_mi=args.lambda_mi,
@@ -208,6 +219,8 @@ def main(argv=None):
         if (epoch + 1) % args.checkpoint_freq == 0 or is_best:
             trainer.save_checkpoint(epoch=epoch, is_best=is_best)
             trainer.save_history(args.checkpoint_dir)
+        if predictor is not None:
+            print(f"  Property loss: train_prop {metrics['train_prop']:.4f}, val_prop {metrics['val_prop']:.4f}")
         if args.verbose:
             print(f"Epoch {epoch + 1}/{args.epochs}: Train Loss: {metrics['train_loss']:.4f}, "
                   f"Val Loss: {metrics['val_loss']:.4f}, Beta: {metrics['beta']:.4f}")

@@ -12,6 +12,11 @@ the running mean, the update has already been applied (Q15); every 25th batch a 
 run for logging with post-update weights and T more coins (Q16).
 Checkpoints: same file names, but a flat non-pickle .npz keyed by the parameter names (Q21).
 
+Property predictor (an extension; the reference's own branch cannot run, Q10): with
+`property_predictor=` a models.PropertyPredictor, the step also trains it (its own Adam, same lr, no bias correction),
+lambda_prop weighs its loss, train_prop / val_prop are real, and the checkpoints carry `predictor_weights/<name>` and
+`predictor_optimizer_state/{m,v}/<name>`.  Not combined with data parallelism (refused).
+
 Data parallelism (the reference is single-process): under `torch.distributed` (train.py started by
 `python -m torch.distributed.run`, one process per GPU) every rank runs THIS epoch flow on the same dataset order and the
 same coins (one seeded NumPy stream), every batch is the GLOBAL batch, and the step / the loss forwards work on the
@@ -44,9 +49,7 @@ class ARCVAETrainerWithLoss:
                  beta_warmup_epochs: int = 100, lambda_prop: float = 0.1, lambda_collapse: float = 0.01,
                  free_bits: float = 0.5, lambda_mi: float = 0.01, grad_clip: float = 1.0,
                  checkpoint_dir: str = "./checkpoints", progress: bool = True):
-        if property_predictor is not None:
-            raise NotImplementedError("property_predictor is unreachable in the reference (Q10)")
-        self.encoder, self.decoder, self.property_predictor = encoder, decoder, None
+        self.encoder, self.decoder, self.property_predictor = encoder, decoder, property_predictor
         self.dataset, self.batch_size, self.grad_clip = dataset, batch_size, grad_clip
         self.lambda_prop, self.lambda_collapse = lambda_prop, lambda_collapse
         self.free_bits, self.lambda_mi = free_bits, lambda_mi
@@ -72,7 +75,7 @@ class ARCVAETrainerWithLoss:
 
     # ---- the three calls into the step engine (tests drive the same epoch flow with oracle-backed ones) ----------
     def _make_engine(self, encoder, decoder):
-        return api.engine_for(encoder, decoder)
+        return api.engine_for(encoder, decoder, self.property_predictor)
 
     def _rank_world(self) -> Tuple[int, int]:
         dp = api.data_parallel_of(self.encoder, self.decoder)
@@ -82,7 +85,8 @@ class ARCVAETrainerWithLoss:
         """loss + grads + (no-op clip, Q6) + both Adam updates: one captured step (N ranks: arcvae_hip.dp).  Returns
         [total_loss, step status] of the GLOBAL batch as one tensor: read together, one host sync per batch."""
         out, _ = api.value_and_grad(self.encoder, self.decoder, molecules, conditions,
-                                    teacher_forcing_ratio=teacher_forcing_ratio, lr=self.learning_rate, **hyper)
+                                    teacher_forcing_ratio=teacher_forcing_ratio, lr=self.learning_rate,
+                                    predictor=self.property_predictor, **hyper)
         return out["loss_and_status"]
 
     def _encode(self, molecules, conditions):
@@ -99,11 +103,14 @@ class ARCVAETrainerWithLoss:
 
     # ---- helpers -------------------------------------------------------------------------------
     def _hyper(self, beta: float) -> Dict[str, float]:
-        return dict(beta=beta, lambda_collapse=self.lambda_collapse, lambda_mi=self.lambda_mi, target_mi=4.85,
-                    free_bits=self.free_bits)
+        h = dict(beta=beta, lambda_collapse=self.lambda_collapse, lambda_mi=self.lambda_mi, target_mi=4.85,
+                 free_bits=self.free_bits)
+        if self.property_predictor is not None:
+            h["lambda_prop"] = self.lambda_prop
+        return h
 
     def _loss_dict(self, molecules, conditions, beta: float, tf: float) -> Dict[str, torch.Tensor]:
-        return complete_vae_loss(self.encoder, self.decoder, None, molecules, conditions, beta=beta,
+        return complete_vae_loss(self.encoder, self.decoder, self.property_predictor, molecules, conditions, beta=beta,
                                  lambda_prop=self.lambda_prop, lambda_collapse=self.lambda_collapse,
                                  teacher_forcing_ratio=tf, free_bits=self.free_bits, lambda_mi=self.lambda_mi,
                                  target_mi=4.85)
@@ -222,6 +229,12 @@ class ARCVAETrainerWithLoss:
         return float(max(s[2 * Z] / f(B) - agg, f(0.0)))
 
     # ---- checkpoints / history (trainer.py:577-736) -----------------------------------------------------
+    def _modules(self):
+        mods = [("encoder", self.encoder), ("decoder", self.decoder)]
+        if self.property_predictor is not None:
+            mods.append(("predictor", self.property_predictor))
+        return mods
+
     def save_checkpoint(self, epoch: int, is_best: bool = False):
         if self.poisoned:
             raise RuntimeError("a training step lost its stream order (encoder and decoder may be one update apart): "
@@ -229,7 +242,7 @@ class ARCVAETrainerWithLoss:
         if self.rank != 0:       # N ranks hold identical weights and optimizer state: rank 0 writes
             return
         ck = {"epoch": np.array(epoch), "history_json": np.array(json.dumps(self.history))}
-        for tag, mod in (("encoder", self.encoder), ("decoder", self.decoder)):
+        for tag, mod in self._modules():
             st = mod.store
             for n in st.names():
                 ck[f"{tag}_weights/{n}"] = st.p(n).cpu().numpy()
@@ -249,7 +262,7 @@ class ARCVAETrainerWithLoss:
 
     def load_checkpoint(self, checkpoint_path: str) -> int:
         ck = np.load(checkpoint_path, allow_pickle=False)
-        for tag, mod in (("encoder", self.encoder), ("decoder", self.decoder)):
+        for tag, mod in self._modules():     # (a checkpoint without predictor_* keys leaves the predictor as it is)
             st = mod.store
             for n in st.names():
                 if f"{tag}_weights/{n}" in ck:
