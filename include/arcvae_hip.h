@@ -439,6 +439,29 @@ int arcvae_prop_backward(const float* z, const float* cond, const float* eps, co
 int arcvae_prop_wgrad(const float* z, const float* ws, long ws_floats, const float* hyper, float* dW1, float* db1,
                       float* dW2, float* db2, float* scalars, int B, int Z, int C, int Hp, arcvae_stream_t stream);
 
+/* ---- opt-in global-norm gradient clipping (an extension: the reference's _clip_gradients, trainer.py:490-522, sums nothing, Q6) --
+ * The reference's intended rule: norm = sqrt(sum g^2) over every gradient the step applies; when norm > max_norm (a NaN norm
+ * compares false) every gradient is multiplied by scale = max_norm / (norm + 1e-8), rounded once to fp32, before the Adam update
+ * above.  Step 1, per store: arcvae_grad_sumsq writes P fp32 partial sums of g^2 (P and the element-to-partial assignment depend
+ * on n alone: bitwise repeatable, aligned or not).  Step 2, per store: the clipped update -- every block sums ALL n_partials
+ * partials of all stores (one buffer, one fixed order) and applies gs = g * scale with the un-bias-corrected Adam on gs; the
+ * gradients are not written.  When `scalars` is non-null, block 0 writes the pre-clip norm to scalars[11] and the applied scale
+ * (1 when not clipping) to scalars[12]; NaN in both when a guard word is set (the update is skipped, as above).
+ * ARCVAE_ERR_ARG before any launch: null pointers, n <= 0, partials_cap < P, n_partials outside [1, 4096], max_norm <= 0 or
+ * not finite. */
+/* P = min(256, ceil(ceil(n / 4) / 256)) partials for n floats, n >= 1. */
+int arcvae_grad_sumsq_partials(long n, long* count);
+int arcvae_grad_sumsq(const float* grads, long n, float* partials, long partials_cap, arcvae_stream_t stream);
+int arcvae_adam_update_clipped(float* params, const float* grads, float* m, float* v, long n, double lr, double beta1,
+                               double beta2, double eps, const unsigned* guard_a, const unsigned* guard_b,
+                               const float* partials, long n_partials, double max_norm, float* scalars, arcvae_stream_t stream);
+/* arcvae_adam_update_finalize with the clip (scalars required: the loss scalars and scalars[11..12]). */
+int arcvae_adam_update_finalize_clipped(float* params, const float* grads, float* m, float* v, long n, double lr,
+                                        double beta1, double beta2, double eps, const unsigned* guard_a,
+                                        const unsigned* guard_b, const float* rowloss, int B, float* stats, float* scalars,
+                                        int Z, int T, const float* partials, long n_partials, double max_norm,
+                                        arcvae_stream_t stream);
+
 /* ---- small helpers ---------------------------------------------------------------------------------- */
 int arcvae_colsum_accum(const float* X, int rows, int cols, int ld, float* out, float scale,
                         arcvae_stream_t stream);

@@ -111,6 +111,11 @@ SIGNATURES = {
     "arcvae_prop_forward": [_vp] * 10 + [_l, _i, _i, _i, _i, _vp],
     "arcvae_prop_backward": [_vp] * 14 + [_l, _i, _i, _i, _i, _vp],
     "arcvae_prop_wgrad": [_vp, _vp, _l] + [_vp] * 6 + [_i, _i, _i, _i, _vp],
+    "arcvae_grad_sumsq_partials": [_l, _lp],
+    "arcvae_grad_sumsq": [_vp, _l, _vp, _l, _vp],
+    "arcvae_adam_update_clipped": [_vp, _vp, _vp, _vp, _l, _d, _d, _d, _d, _vp, _vp, _vp, _l, _d, _vp, _vp],
+    "arcvae_adam_update_finalize_clipped": [_vp, _vp, _vp, _vp, _l, _d, _d, _d, _d, _vp, _vp, _vp, _i, _vp, _vp, _i, _i,
+                                            _vp, _l, _d, _vp],
 }
 
 LONG_RESULTS = {"arcvae_enc_lstm_bwd_rs_part_floats"}      # size queries returning `long`; everything else returns an int code

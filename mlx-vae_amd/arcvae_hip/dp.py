@@ -167,19 +167,28 @@ class EngineOps:
     Event form (fallback when the gate probe fails, ARCVAE_GATES=0): as in round 1 --
       side: [dec_fwd] -> ev_chain -> [dec_bwd] -> ev_dec_bwd;  comm stream: CE sum and dec.grad reduced beside the
       BPTT sweep;  enc.grad reduced after it.
+
+    Global-norm clip (clip = max_norm): the norm is taken over the REDUCED (global) gradients.  Every
+    rank holds the same all-reduced buckets and runs the same sum-of-squares kernels over them (partials fixed by the buffer
+    length alone), so every rank derives the same norm and scale with no collective of its own.  Early form: the decoder's sum
+    of squares replaces its Adam update on side, behind the decoder bucket's reduce; the finish forms the encoder's after the
+    late bucket and applies both clipped updates.  Late and event forms: both sums of squares in the finish.
     """
 
     def __init__(self, engine, ws, lr: float, global_rows: int, use_graph: bool = True,
-                 group: Optional[dist.ProcessGroup] = None):
+                 group: Optional[dist.ProcessGroup] = None, clip: Optional[float] = None):
         """group: the communicator of the DataParallelStep this ops object will be driven by (None = the default group).  The
         two collectives issued HERE -- the warm-up and the agreement on the gated / event form -- run on it: with a subgroup,
         ranks outside it never construct an EngineOps, and a collective on the default group would hang."""
         self.eng, self.ws, self.lr = engine, ws, float(lr)
         self.group = group
         self.global_rows = int(global_rows)
+        self.clip = clip                 # global-norm clip's max_norm, or None
+        if clip is not None:
+            engine.clip_workspace(ws)
         Z = engine.d.Z
         self.stats = ws.stats[:2 * Z + 3]
-        self.run = engine.runner(ws, lr, global_rows, capture=use_graph)
+        self.run = engine.runner(ws, lr, global_rows, capture=use_graph, clip=clip)
         if dist.is_initialized() and dist.get_backend() == "nccl":
             # warm the communicator up (channel / IPC set-up of the first collective can take seconds on 8 GPUs) before
             # any gate kernel can be left spinning behind it
@@ -260,7 +269,7 @@ class EngineOps:
             eng._dp_bucket = cur
             eng._runners.clear()
             eng._graphs.clear()
-            self.run = eng.runner(self.ws, self.lr, self.global_rows, capture=self.run.capture)
+            self.run = eng.runner(self.ws, self.lr, self.global_rows, capture=self.run.capture, clip=self.clip)
         self.bucket = cur
         nh = eng.enc.offsets["condition_fc.weight"]   # the heads' parameters are the tail of the encoder's flat buffer (store.py)
         self.bucket_enc = cur[:ne]               # complete after the join (last weight-gradient chunk)
@@ -296,6 +305,11 @@ class EngineOps:
         eng, ws = self.eng, self.ws
         self.run("dp_dec_adam", lambda: adam_update(eng.dec, self.lr, guards=eng.guards(ws)), torch.cuda.current_stream())
 
+    def _dec_sumsq_gated(self) -> None:
+        from .engine import grad_sumsq
+        eng, ws = self.eng, self.ws
+        self.run("dp_dec_sumsq", lambda: grad_sumsq(eng.dec, ws, "dec"), torch.cuda.current_stream())
+
     def _join_gated(self) -> None:
         self.run("dp_join", self.eng.gates.join, torch.cuda.current_stream())  # aux and side reported their last piece
 
@@ -308,6 +322,14 @@ class EngineOps:
             ws.stats[2 * Z + 3:2 * Z + 4].copy_(self.bucket_recon)   # GLOBAL CE sum (side reduced it long ago)
             ga, gb = eng.guards(ws)
             call("arcvae_loss_finalize", ptr(ws.stats), ptr(ws.scalars), Z, ws.T, ga, gb, stream_ptr())
+            if self.clip is not None:
+                from .engine import adam_update_clipped, grad_sumsq
+                if not self.early:                                    # (early form: side formed the decoder's already)
+                    grad_sumsq(eng.dec, ws, "dec")
+                grad_sumsq(eng.enc, ws, "enc")
+                adam_update_clipped(eng.dec, self.lr, ws, self.clip, (ga, gb))
+                adam_update_clipped(eng.enc, self.lr, ws, self.clip, (ga, gb), scalars=ws.scalars)
+                return
             if not self.early:                                        # (early form: the decoder's update rode on side)
                 adam_update(eng.dec, self.lr, guards=(ga, gb))
             adam_update(eng.enc, self.lr, guards=(ga, gb))
@@ -355,7 +377,11 @@ class EngineOps:
 
     def early_done(self) -> None:
         if self.gated and self.early:
-            self._dec_adam_gated()                   # decoder gradients are GLOBAL: its Adam update rides on side too
+            # decoder gradients are GLOBAL: its Adam update rides on side too -- or, with the clip, its sum of squares
+            if self.clip is not None:
+                self._dec_sumsq_gated()
+            else:
+                self._dec_adam_gated()
 
     @property
     def seam_issue_early(self) -> bool:
@@ -401,7 +427,7 @@ class EngineOps:
             self._finish_gated()
             return
         torch.cuda.current_stream().wait_stream(self.comm)
-        self.eng.enqueue_finish(self.ws, self.lr, True, self.run)
+        self.eng.enqueue_finish(self.ws, self.lr, True, self.run, clip=self.clip)
 
 
 def agree_all(flag: bool, group: Optional[dist.ProcessGroup], device) -> bool:
@@ -475,24 +501,29 @@ class EngineDataParallel:
     def _load(self, ws, x, cond, eps, coins, lo, hi):
         self.eng.load_inputs(ws, x[lo:hi], cond[lo:hi], None if eps is None else eps[lo:hi], coins)
 
-    def train_step(self, x, cond, eps, coins, lr: float, **hyper):
+    def train_step(self, x, cond, eps, coins, lr: float, clip_norm: Optional[float] = None, **hyper):
         """Loss, gradients and both Adam updates for the GLOBAL batch (x, cond, eps: all rows, identical on every rank;
         eps may also be this rank's own draw of the right shape: no loss value depends on it, Q2).  Returns the local
-        workspace: ws.scalars are the global batch's loss scalars."""
+        workspace: ws.scalars are the global batch's loss scalars.  clip_norm: the global-norm clip of the global gradients
+        (EngineOps; ws.scalars[11] / [12] = its norm and scale, the same on every rank)."""
+        from .engine import check_clip_norm
+        clip = check_clip_norm(clip_norm)
         eng = self.eng
         n, T = int(x.shape[0]), int(x.shape[1])
         lo, hi, replicated = self.bounds(n)
         if replicated:       # fewer rows than ranks: the single-process step on every rank, then rank 0's state everywhere
-            eng.train_step(x, cond, eps, coins, lr=lr, update=True, **hyper)
+            eng.train_step(x, cond, eps, coins, lr=lr, update=True, clip_norm=clip, **hyper)
             self._broadcast_state()
             return eng.workspace(n, T, train=True)
         ws = eng.workspace(hi - lo, T, train=True)
         eng.set_hyper(ws, **hyper)
         self._load(ws, x, cond, eps, coins, lo, hi)
         key = (hi - lo, T, n, float(lr), float(eng.hyper_host["free_bits"]))
+        if clip is not None:
+            key += (clip,)
         drv = self._drivers.get(key)
         if drv is None:
-            ops = EngineOps(eng, ws, lr, n, use_graph=(eng.mode != "eager"), group=self.group)
+            ops = EngineOps(eng, ws, lr, n, use_graph=(eng.mode != "eager"), group=self.group, clip=clip)
             drv = DataParallelStep(ops, self.group, early_group=self._early_group)
             self._early_group = drv.early_group
             self._drivers[key] = drv

@@ -6,7 +6,8 @@ MLX Adam updates.  Here the same step is a fixed sequence of launches on three H
 
   main stream : tokens^T -> table0 GEMM -> LSTM wavefront sweep -> heads -> [stats seam]
                 -> latent loss -> heads dcomb chain -> BPTT wavefront -> join -> Adam      (the dependent chain)
-  side stream : dense decoder fwd (B*V rows) -> TF walk + CE -> dlogits -> dense decoder bwd -> its Adam;
+  side stream : dense decoder fwd (B*V rows) -> TF walk + CE -> dlogits -> dense decoder bwd -> its Adam (with the opt-in
+                global-norm clip: its sum of squares, the update moves into main's finish -- DESIGN.md section 7);
                 at the end the token-table half of the last weight-gradient chunk
   aux stream  : parameter-gradient GEMMs of the encoder, chunk by chunk behind the BPTT sweep
 
@@ -915,6 +916,33 @@ def adam_update(store: ParamStore, lr: float, b1: float = 0.9, b2: float = 0.999
          C.c_long(store.numel_padded), float(lr), float(b1), float(b2), float(eps), guards[0], guards[1], stream_ptr())
 
 
+def check_clip_norm(clip_norm) -> Optional[float]:
+    """None (no clipping) or the max_norm of the global-norm clip as a float: > 0 and finite, else ValueError."""
+    if clip_norm is None:
+        return None
+    c = float(clip_norm)
+    if not (c > 0.0 and np.isfinite(c)):
+        raise ValueError(f"the clip norm must be > 0 and finite, got {clip_norm!r}")
+    return c
+
+
+def grad_sumsq(store: ParamStore, ws: Workspace, which: str) -> None:
+    """Global-norm clip, step 1 (csrc/clip.hip): the store's partial sums of g^2 into its slice of ws.clip_part
+    (StepEngine.clip_workspace).  Over the padded flat buffer: the padding gradients are zero (no kernel writes them)."""
+    off, cnt = ws.clip_off[which]
+    call("arcvae_grad_sumsq", ptr(store.grad), C.c_long(store.numel_padded), C.c_void_p(ws.clip_part.data_ptr() + 4 * off),
+         C.c_long(cnt), stream_ptr())
+
+
+def adam_update_clipped(store: ParamStore, lr: float, ws: Workspace, clip_norm: float, guards=NO_GUARDS,
+                        scalars: Optional[torch.Tensor] = None) -> None:
+    """Global-norm clip, step 2: adam_update on g * scale, the scale derived in every block from ALL partials of ws.clip_part
+    (every store's sum of squares must precede it).  scalars (optional): [11] = the pre-clip norm, [12] = the applied scale."""
+    call("arcvae_adam_update_clipped", ptr(store.flat), ptr(store.grad), ptr(store.adam_m), ptr(store.adam_v),
+         C.c_long(store.numel_padded), float(lr), 0.9, 0.999, 1e-8, guards[0], guards[1], ptr(ws.clip_part),
+         C.c_long(ws.clip_part.numel()), float(clip_norm), ptr(scalars), stream_ptr())
+
+
 # --------------------------------------------------------------------------------------------
 class StepEngine:
     """Owns workspaces, streams and captured launch segments for one (encoder, decoder) pair.
@@ -1002,7 +1030,9 @@ class StepEngine:
         decoder's own segment, ~1 ms before the sweeps finish: it is skipped when the words are already set by then (a
         failure of an earlier step, a forward sweep that gave up), but a word raised later in the same step finds it
         applied -- the two modules are then one update apart, which is why the trainer stops at that batch and refuses
-        to checkpoint (`step_status`, read with the per-batch loss; `check_gates`)."""
+        to checkpoint (`step_status`, read with the per-batch loss; `check_gates`).  With the global-norm clip on
+        (train_step(clip_norm=)) every update runs in the finish and reads the words at the same point: the modules
+        cannot be a step apart then (the trainer's handling stays the same for both)."""
         ga = self.gates.word(Gates.ERR) if self.gates is not None else C.c_void_p(0)
         return ga, C.c_void_p(ws.psync.data_ptr() + 4 * 500)
 
@@ -1012,6 +1042,21 @@ class StepEngine:
         L = self.d.L
         ws.trace_fwd = torch.zeros(2 * (ws.T + L + 1), dtype=torch.int64, device=self.device)
         ws.trace_bwd = torch.zeros(2 * (ws.T + 2 * L + 2), dtype=torch.int64, device=self.device)
+
+    def clip_workspace(self, ws: Workspace) -> None:
+        """The partials of the global-norm clip: ws.clip_part = [encoder | decoder | predictor] slices of
+        arcvae_grad_sumsq_partials(numel_padded) floats each (ws.clip_off: name -> (offset, count))."""
+        if getattr(ws, "clip_part", None) is not None:
+            return
+        lib, off, ws.clip_off = _lib.load(), 0, {}
+        for name, st in (("enc", self.enc), ("dec", self.dec), ("prop", self.prop)):
+            if st is None:
+                continue
+            n = C.c_long(0)
+            _lib.check(lib.arcvae_grad_sumsq_partials(C.c_long(st.numel_padded), C.byref(n)), "arcvae_grad_sumsq_partials")
+            ws.clip_off[name] = (off, n.value)
+            off += n.value
+        ws.clip_part = torch.zeros(off, dtype=torch.float32, device=self.device)
 
     def check_gates(self) -> None:
         """Raise if a gate ever gave up waiting (results after that point are not ordered).  Host sync."""
@@ -1148,8 +1193,11 @@ class StepEngine:
             ck = torch.as_tensor(np.asarray(coins).astype(np.uint8))
             ws.coins.copy_(ck.to(dev))
 
-    def runner(self, ws: Workspace, lr: float, global_rows: int, capture: bool) -> SegmentRunner:
+    def runner(self, ws: Workspace, lr: float, global_rows: int, capture: bool, clip: Optional[float] = None) -> SegmentRunner:
+        # (clip: segments recorded with the clip's order are never replayed without it, nor the reverse)
         key = (ws.B, ws.T, float(lr), float(self.hyper_host["free_bits"]), int(global_rows), bool(capture))
+        if clip is not None:
+            key += (float(clip),)
         if key not in self._runners:
             self._runners[key] = SegmentRunner(capture)
         return self._runners[key]
@@ -1157,9 +1205,10 @@ class StepEngine:
     # ---- the phases of a step (data-parallel collectives go between them, dp.py) ------------------------
     def enqueue_decoder(self, ws: Workspace, global_rows: int, run=_inline, backward: bool = True,
                         wait_current: bool = True, split_events: bool = True, gate=None,
-                        adam_lr: Optional[float] = None) -> None:
+                        adam_lr: Optional[float] = None, clip_sumsq: bool = False) -> None:
         """Dense decoder on the side stream: forward + TF walk + CE row sums (ev_chain), then its whole backward
-        (ev_dec_bwd).  Independent of the encoder (Q2); it only has to follow the input copies."""
+        (ev_dec_bwd).  Independent of the encoder (Q2); it only has to follow the input copies.  clip_sumsq: the
+        backward ends with the decoder's sum of squares of the global-norm clip (its update then runs in the finish)."""
         d = self.d
         if wait_current:
             self.side.wait_stream(torch.cuda.current_stream())
@@ -1176,6 +1225,8 @@ class StepEngine:
             decoder_backward(self.dec, ws, d, 1.0 / (global_rows * ws.T))
             if adam_lr is not None:
                 adam_update(self.dec, adam_lr, guards=self.guards(ws))
+            if clip_sumsq:
+                grad_sumsq(self.dec, ws, "dec")
             if gate is not None:
                 # decoder gradients and CE row sums of this step are complete (read by the data-parallel step, which
                 # reduces them early; raised in every gated step so that D stays in lockstep with main's step count)
@@ -1240,24 +1291,50 @@ class StepEngine:
         call("arcvae_stats_set_recon", ptr(ws.rowloss), ws.B, ptr(ws.stats), self.d.Z, stream_ptr())
 
     def enqueue_finish(self, ws: Workspace, lr: float, update: bool, run=_inline, with_recon: bool = False,
-                       dec_adam: bool = True, join_side: bool = True, gates: Optional[Gates] = None) -> None:
+                       dec_adam: bool = True, join_side: bool = True, gates: Optional[Gates] = None,
+                       clip: Optional[float] = None, dec_sumsq: bool = True) -> None:
         """[join ->] [CE sum ->] recon/total scalars, both Adam updates: one segment."""
         main = torch.cuda.current_stream()
         if join_side:
             main.wait_stream(self.side)
 
-        fin = self._finish_ops(ws, lr, update, with_recon, dec_adam, gates)
+        fin = self._finish_ops(ws, lr, update, with_recon, dec_adam, gates, clip, dec_sumsq)
         run(("finish" if update else "finish_noupdate") + ("_r" if with_recon else ""), fin, main)
 
-    def _finish_ops(self, ws: Workspace, lr: float, update: bool, with_recon: bool, dec_adam: bool, gates: Optional[Gates]):
-        """The launches of a step's finish as a closure (its own segment, or the end of the main segment: _enqueue_step)."""
+    def _finish_ops(self, ws: Workspace, lr: float, update: bool, with_recon: bool, dec_adam: bool, gates: Optional[Gates],
+                    clip: Optional[float] = None, dec_sumsq: bool = True):
+        """The launches of a step's finish as a closure (its own segment, or the end of the main segment: _enqueue_step).
+        clip (the global-norm clip's max_norm, with update): after the join the remaining sums of squares (the encoder's; the
+        decoder's unless dec_sumsq=False, i.e. side formed it at the end of its backward), then the clipped updates of ALL
+        stores -- the decoder's too, whatever dec_adam says."""
+        clip = clip if update else None
+
         def fin():
             if self.prop is not None:
                 # the predictor's gradients and loss scalars: main is idle here while aux / side finish the step's tail
                 prop_wgrad(self.prop, ws, self.d, self.prop_hidden)
+                if clip is not None:
+                    grad_sumsq(self.prop, ws, "prop")
             if gates is not None:
                 gates.join()
             ga, gb = self.guards(ws)
+            if clip is not None:
+                if dec_sumsq:
+                    grad_sumsq(self.dec, ws, "dec")
+                grad_sumsq(self.enc, ws, "enc")
+                adam_update_clipped(self.dec, lr, ws, clip, (ga, gb))
+                if with_recon:
+                    st = self.enc
+                    call("arcvae_adam_update_finalize_clipped", ptr(st.flat), ptr(st.grad), ptr(st.adam_m), ptr(st.adam_v),
+                         C.c_long(st.numel_padded), float(lr), 0.9, 0.999, 1e-8, ga, gb, ptr(ws.rowloss), ws.B, ptr(ws.stats),
+                         ptr(ws.scalars), self.d.Z, ws.T, ptr(ws.clip_part), C.c_long(ws.clip_part.numel()), float(clip),
+                         stream_ptr())
+                else:
+                    call("arcvae_loss_finalize", ptr(ws.stats), ptr(ws.scalars), self.d.Z, ws.T, ga, gb, stream_ptr())
+                    adam_update_clipped(self.enc, lr, ws, clip, (ga, gb), scalars=ws.scalars)
+                if self.prop is not None:
+                    adam_update_clipped(self.prop, lr, ws, clip, (ga, gb))
+                return
             if with_recon and update:
                 # CE sum + recon / total scalars ride in block 0 of the encoder's Adam launch (round 4: one launch less in the tail)
                 if dec_adam:
@@ -1282,11 +1359,15 @@ class StepEngine:
                     adam_update(self.prop, lr, guards=(ga, gb))
         return fin
 
-    def _enqueue_step(self, ws: Workspace, lr: float, global_rows: int, update: bool, run=_inline) -> None:
+    def _enqueue_step(self, ws: Workspace, lr: float, global_rows: int, update: bool, run=_inline,
+                      clip: Optional[float] = None) -> None:
         """Single-process step.  Host enqueue order: the decoder segment (one short graph launch; it overlaps the
         forward sweep, whose launches leave CUs idle at every seam), the encoder forward, then the fused loss +
         dcomb + BPTT segments with the weight-gradient chunks on aux; the decoder is only joined at the very end
-        (nothing on the encoder's backward path needs the reconstruction term)."""
+        (nothing on the encoder's backward path needs the reconstruction term).
+        clip (global-norm clip, with update): the decoder's update leaves side, whose segment ends with the decoder's sum of
+        squares instead; the finish applies every clipped update after the join (_finish_ops) -- on every path below."""
+        clip = clip if update else None
         main = torch.cuda.current_stream()
         if self.mode != "graph" and self._gating_ok(main):
             g = self.gates
@@ -1309,7 +1390,7 @@ class StepEngine:
             # gradients are complete ~1 ms before the encoder's): one launch less in the exposed tail of the step.
             def dec_after_main():
                 self.enqueue_decoder(ws, global_rows, grun, wait_current=False, split_events=False, gate=(g, nc < 2),
-                                     adam_lr=lr if update else None)
+                                     adam_lr=lr if (update and clip is None) else None, clip_sumsq=clip is not None)
 
             # From a runner's second step on, the finish rides at the end of the main segment (ARCVAE_MERGE_FINISH=0: never).  Not
             # in its first step -- that one runs every segment eagerly and synchronises, and the finish begins with a join that aux
@@ -1320,19 +1401,20 @@ class StepEngine:
             merged = (nc >= 2 and steps_done >= 1 and getattr(run, "capture", False)
                       and not fused_wgrad_ok(ws, self.d) and os.environ.get("ARCVAE_MERGE_FINISH", "1") != "0")
             if merged:
-                fin = self._finish_ops(ws, lr, update, True, False, g)
+                fin = self._finish_ops(ws, lr, update, True, False, g, clip, dec_sumsq=False)
                 self.enqueue_backward(ws, grun_e, gates=g, fuse_forward=True, after_first=dec_after_main,
                                       start_signal=g.word(g.P), epilogue=fin)
                 return
             self.enqueue_backward(ws, grun, gates=g, fuse_forward=True, after_first=dec_after_main,
                                   start_signal=g.word(g.P))
-            self.enqueue_finish(ws, lr, update, grun, with_recon=True, dec_adam=False, join_side=False, gates=g)
+            self.enqueue_finish(ws, lr, update, grun, with_recon=True, dec_adam=False, join_side=False, gates=g, clip=clip,
+                                dec_sumsq=False)
             return
         self.side.wait_stream(main)                          # the decoder only has to follow the input copies
-        self.enqueue_decoder(ws, global_rows, run, wait_current=False, split_events=False)
+        self.enqueue_decoder(ws, global_rows, run, wait_current=False, split_events=False, clip_sumsq=clip is not None)
         self.enqueue_encoder_forward(ws, run)
         self.enqueue_backward(ws, run)
-        self.enqueue_finish(ws, lr, update, run, with_recon=True)
+        self.enqueue_finish(ws, lr, update, run, with_recon=True, clip=clip, dec_sumsq=False)
 
     # ---- public API --------------------------------------------------------------------------------
     def forward_loss(self, x, cond, eps, coins, **hyper) -> Dict[str, torch.Tensor]:
@@ -1354,38 +1436,51 @@ class StepEngine:
         torch.cuda.current_stream().wait_stream(self.side)
         return self._results(ws)
 
-    def train_step(self, x, cond, eps, coins, lr: float, update: bool = True, **hyper) -> Dict[str, torch.Tensor]:
-        """loss + grads (+ Adam) for one minibatch; single process (see dp.py for N ranks)."""
+    def train_step(self, x, cond, eps, coins, lr: float, update: bool = True, clip_norm: Optional[float] = None,
+                   **hyper) -> Dict[str, torch.Tensor]:
+        """loss + grads (+ Adam) for one minibatch; single process (see dp.py for N ranks).  clip_norm (opt-in, DESIGN.md
+        section 10): the updates apply the global-norm clip with that max_norm; the result then also holds "grad_norm" (the
+        pre-clip norm) and "clip_scale" (the applied scale, 1 when not clipping).  store.grad keeps the unclipped gradients."""
+        clip = check_clip_norm(clip_norm)
+        if clip is not None and not update:
+            raise ValueError("clip_norm needs an update to clip (update=True, with lr)")
         B, T = int(x.shape[0]), int(x.shape[1])
         ws = self.workspace(B, T, train=True)
         self.set_hyper(ws, **hyper)
         self.load_inputs(ws, x, cond, eps, coins)
-        self.run_step(ws, lr, update)
-        return self._results(ws)
+        self.run_step(ws, lr, update, clip_norm=clip)
+        return self._results(ws, clip=clip is not None)
 
-    def run_step(self, ws: Workspace, lr: float, update: bool = True) -> None:
+    def run_step(self, ws: Workspace, lr: float, update: bool = True, clip_norm: Optional[float] = None) -> None:
         """Enqueue (or replay) the step on the current stream; inputs/hyper already in `ws`."""
+        clip = check_clip_norm(clip_norm) if update else None
+        if clip is not None:
+            self.clip_workspace(ws)
         if self.mode == "graph":
             key = (ws.B, ws.T, float(lr), float(self.hyper_host["free_bits"]), bool(update))
+            if clip is not None:             # a graph captured without the clip is never replayed with it
+                key += (clip,)
             g = self._graphs.get(key)
             if g is None:
                 self._enqueue_step(ws, lr, ws.B, False)  # warm-up once eagerly, then capture
                 torch.cuda.synchronize()
                 g = torch.cuda.CUDAGraph()
                 with torch.cuda.graph(g):
-                    self._enqueue_step(ws, lr, ws.B, update)
+                    self._enqueue_step(ws, lr, ws.B, update, clip=clip)
                 self._graphs[key] = g
             g.replay()
             return
-        run = self.runner(ws, lr, ws.B, capture=(self.mode == "segments"))
+        run = self.runner(ws, lr, ws.B, capture=(self.mode == "segments"), clip=clip)
         if not update:  # gradient-only steps (tests, value_and_grad without lr) use their own segment set
             run = self.runner(ws, -1.0, ws.B, capture=(self.mode == "segments"))
-        self._enqueue_step(ws, lr, ws.B, update, run)
+        self._enqueue_step(ws, lr, ws.B, update, run, clip=clip)
 
-    def _results(self, ws: Workspace) -> Dict[str, torch.Tensor]:
+    def _results(self, ws: Workspace, clip: bool = False) -> Dict[str, torch.Tensor]:
         out = {k: ws.scalars[i] for i, k in enumerate(SCALAR_KEYS)}
         out["mu"], out["logvar"], out["z"] = ws.mu, ws.logvar, ws.z
         out["step_status"] = ws.scalars[15]   # 1.0: a gate expired / a persistent sweep gave up (values NaN, no update)
+        if clip:
+            out["grad_norm"], out["clip_scale"] = ws.scalars[11], ws.scalars[12]   # NaN, NaN when the update was skipped
         return out
 
     def gather_logits(self, ws: Workspace) -> torch.Tensor:

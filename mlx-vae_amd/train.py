@@ -68,6 +68,9 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--dist_backend", choices=["nccl", "gloo"], default="nccl",
                     help="torch.distributed backend (extension): nccl = RCCL over xGMI, one rank per GPU; gloo carries "
                          "device tensors through the host (several ranks on one GPU: tests)")
+    ap.add_argument("--grad_clip_mode", choices=["reference", "global_norm"], default="reference",
+                    help="reference: --grad_clip is a no-op, as in the reference (Q6); global_norm: clip the step's "
+                         "gradients to the global norm --grad_clip (<= 0: no clipping; extension)")
     ap.add_argument("--property_predictor_hidden", type=int, default=0,
                     help="hidden width of a property predictor on z trained with --lambda_prop (extension; 0 = no predictor, "
                          "--lambda_prop is then unused as in the reference)")
@@ -198,7 +201,8 @@ def main(argv=None):
         batch_size=args.batch_size, learning_rate=args.learning_rate, beta_start=args.beta_start,
         beta_end=args.beta_end, beta_warmup_epochs=args.beta_warmup_epochs, lambda_prop=args.lambda_prop,
         lambda_collapse=args.lambda_collapse, free_bits=args.free_bits, lambda_mi=args.lambda_mi,
-        grad_clip=args.grad_clip, checkpoint_dir=args.checkpoint_dir, progress=not args.no_progress)
+        grad_clip=args.grad_clip, checkpoint_dir=args.checkpoint_dir, progress=not args.no_progress,
+        grad_clip_mode=args.grad_clip_mode)
     if args.resume:
         loaded = trainer.load_checkpoint(str(checkpoint_dir / "checkpoint_best.npz"))
         start_epoch = loaded + 1  # best_val_loss restarts at inf, as in the reference (Q21)
@@ -212,6 +216,8 @@ def main(argv=None):
                   "val_kl", "val_collapse", "val_prop", "beta", "teacher_forcing", "mutual_info"):
             trainer.history[k].append(metrics[k])
         trainer.history["learning_rate"].append(args.learning_rate)
+        if "grad_norm" in trainer.history:       # --grad_clip_mode global_norm: epoch mean of the pre-clip norms
+            trainer.history["grad_norm"].append(metrics["grad_norm"])
         is_best = metrics["val_loss"] < best_val_loss
         if is_best:
             best_val_loss = metrics["val_loss"]

@@ -6,10 +6,16 @@ Q5/Q16), so an epoch visits the same batches with the same coins as the referenc
 step itself (loss, gradients, two un-bias-corrected Adam updates; trainer.py:292-333) is one
 captured hipGraph replay of the arcvae_hip engine.
 
-Reproduced on purpose: gradient clipping is a no-op (Q6: the reference's `_clip_gradients` sums
+Reproduced on purpose: by default gradient clipping is a no-op (Q6: the reference's `_clip_gradients` sums
 nothing, so `grad_clip` never changes a gradient); a "loss explosion" only drops the value from
 the running mean, the update has already been applied (Q15); every 25th batch a second forward is
 run for logging with post-update weights and T more coins (Q16).
+
+Global-norm clipping (an extension): `grad_clip_mode="global_norm"` applies the reference's
+intended rule with max_norm = `grad_clip` (<= 0: no clipping, as the reference's `if self.grad_clip > 0`) inside the
+captured step -- norm over every gradient of the step, predictor included, scale = max_norm / (norm + 1e-8) when the norm
+exceeds max_norm.  `history["grad_norm"]` then holds the epoch mean of the pre-clip norms, read with the per-batch loss
+(no extra host sync).  `grad_clip_mode="reference"` (default) keeps the no-op and the history keys as they are.
 Checkpoints: same file names, but a flat non-pickle .npz keyed by the parameter names (Q21).
 
 Property predictor (an extension; the reference's own branch cannot run, Q10): with
@@ -48,9 +54,14 @@ class ARCVAETrainerWithLoss:
                  batch_size: int = 32, beta_start: float = 0.0, beta_end: float = 0.4,
                  beta_warmup_epochs: int = 100, lambda_prop: float = 0.1, lambda_collapse: float = 0.01,
                  free_bits: float = 0.5, lambda_mi: float = 0.01, grad_clip: float = 1.0,
-                 checkpoint_dir: str = "./checkpoints", progress: bool = True):
+                 checkpoint_dir: str = "./checkpoints", progress: bool = True, grad_clip_mode: str = "reference"):
         self.encoder, self.decoder, self.property_predictor = encoder, decoder, property_predictor
         self.dataset, self.batch_size, self.grad_clip = dataset, batch_size, grad_clip
+        if grad_clip_mode not in ("reference", "global_norm"):
+            raise ValueError(f"grad_clip_mode must be 'reference' or 'global_norm', got {grad_clip_mode!r}")
+        self.grad_clip_mode = grad_clip_mode
+        # max_norm of the step's global-norm clip, or None: the reference's no-op (Q6)
+        self.clip_norm = float(grad_clip) if (grad_clip_mode == "global_norm" and grad_clip > 0) else None
         self.lambda_prop, self.lambda_collapse = lambda_prop, lambda_collapse
         self.free_bits, self.lambda_mi = free_bits, lambda_mi
         self.beta_start, self.beta_end, self.beta_warmup_epochs = beta_start, beta_end, beta_warmup_epochs
@@ -72,6 +83,8 @@ class ARCVAETrainerWithLoss:
             "epoch", "train_loss", "train_recon", "train_kl", "train_collapse", "train_prop", "val_loss",
             "val_recon", "val_kl", "val_collapse", "val_prop", "beta", "teacher_forcing", "learning_rate",
             "mutual_info")}
+        if self.clip_norm is not None:
+            self.history["grad_norm"] = []
 
     # ---- the three calls into the step engine (tests drive the same epoch flow with oracle-backed ones) ----------
     def _make_engine(self, encoder, decoder):
@@ -82,12 +95,13 @@ class ARCVAETrainerWithLoss:
         return (dp.rank, dp.world) if dp is not None else (0, 1)
 
     def _train_step(self, molecules, conditions, teacher_forcing_ratio: float, hyper: Dict[str, float]):
-        """loss + grads + (no-op clip, Q6) + both Adam updates: one captured step (N ranks: arcvae_hip.dp).  Returns
-        [total_loss, step status] of the GLOBAL batch as one tensor: read together, one host sync per batch."""
+        """loss + grads + (no-op clip, Q6, or the global-norm clip) + both Adam updates: one captured step (N ranks:
+        arcvae_hip.dp).  Returns [total_loss, step status] of the GLOBAL batch as one tensor -- [total_loss, step status,
+        pre-clip norm] with the global-norm clip: read together, one host sync per batch."""
         out, _ = api.value_and_grad(self.encoder, self.decoder, molecules, conditions,
                                     teacher_forcing_ratio=teacher_forcing_ratio, lr=self.learning_rate,
-                                    predictor=self.property_predictor, **hyper)
-        return out["loss_and_status"]
+                                    predictor=self.property_predictor, grad_clip=self.clip_norm, **hyper)
+        return out["loss_status_norm"] if self.clip_norm is not None else out["loss_and_status"]
 
     def _encode(self, molecules, conditions):
         return self.encoder(molecules, conditions)
@@ -145,6 +159,7 @@ class ARCVAETrainerWithLoss:
         beta = self.compute_beta(epoch)
         tf = self.compute_teacher_forcing_ratio(epoch, total_epochs)
         self.last_train_metrics = self._train_epoch_batches(beta, tf)
+        extra = {"grad_norm": self.last_train_metrics["grad_norm"]} if "grad_norm" in self.last_train_metrics else {}
         if self.engine is not None:
             self.engine.check_gates()  # a device-side gate that expired would mean the step's streams lost their order
         true_train = self._compute_true_train_loss(epoch, num_batches=20)
@@ -157,7 +172,7 @@ class ARCVAETrainerWithLoss:
             "train_collapse": true_train["collapse"], "train_prop": true_train["prop"],
             "val_loss": val.get("loss", 0.0), "val_recon": val.get("recon", 0.0), "val_kl": val.get("kl", 0.0),
             "val_collapse": val.get("collapse", 0.0), "val_prop": val.get("prop", 0.0), "beta": beta,
-            "teacher_forcing": tf, "mutual_info": mi_value,
+            "teacher_forcing": tf, "mutual_info": mi_value, **extra,
         }
 
     def _train_epoch_batches(self, beta: float, teacher_forcing_ratio: float) -> Dict[str, float]:
@@ -165,22 +180,27 @@ class ARCVAETrainerWithLoss:
         total_loss, num_batches = 0.0, 0
         sums = dict(recon=0.0, kl=0.0, collapse=0.0, prop=0.0)
         comp_count = 0
+        norms = []               # pre-clip norms of the epoch's steps (global-norm clip only)
         hyper = self._hyper(beta)
         it = self.dataset.to_batches(self.batch_size, shuffle=True)
         if self.progress:
             it = tqdm(it, total=len(self.dataset) // self.batch_size, desc="Training batches")
         for batch_idx, (molecules, conditions) in enumerate(it):
             loss_st = self._train_step(molecules, conditions, teacher_forcing_ratio, hyper)
+            nst = int(loss_st.numel())   # 2, or 3 with the global-norm clip's norm
             if batch_idx == 0 or batch_idx % 25 == 0:  # Q16: second forward, post-update weights, T more coins
                 d = self._loss_dict(molecules, conditions, beta, teacher_forcing_ratio)
                 vals = torch.cat([loss_st, torch.stack([d["recon_loss"], d["kl_loss"], d["collapse_penalty"],
                                                         d["prop_loss"]])]).tolist()
                 loss_val, status = vals[0], vals[1]
-                for k, v in zip(("recon", "kl", "collapse", "prop"), vals[2:]):
+                for k, v in zip(("recon", "kl", "collapse", "prop"), vals[nst:]):
                     sums[k] += v
                 comp_count += 1
             else:
-                loss_val, status = loss_st.tolist()  # the reference syncs here too (trainer.py:366)
+                vals = loss_st.tolist()  # the reference syncs here too (trainer.py:366)
+                loss_val, status = vals[0], vals[1]
+            if nst == 3:
+                norms.append(vals[2])
             if status != 0.0:
                 # a device-side gate expired or a persistent sweep gave up in THIS step: the device has already
                 # skipped both Adam updates (the weights are those of the previous batch); stop here, not at epoch end
@@ -197,13 +217,18 @@ class ARCVAETrainerWithLoss:
                 continue
             total_loss += loss_val
             num_batches += 1
-        return {"loss": total_loss / max(1, num_batches),
-                **{k: (v / comp_count if comp_count > 0 else 0.0) for k, v in sums.items()}}
+        out = {"loss": total_loss / max(1, num_batches),
+               **{k: (v / comp_count if comp_count > 0 else 0.0) for k, v in sums.items()}}
+        if self.clip_norm is not None:
+            out["grad_norm"] = float(np.mean(norms)) if norms else 0.0
+        return out
 
     @staticmethod
     def _clip_gradients(grads, max_norm: float = 1.0) -> Tuple:
         """trainer.py:490-522 sums only top-level arrays of the two grad trees; every top-level entry is a
-        sub-module dict, so the norm is 0 and the gradients are returned unchanged (Q6)."""
+        sub-module dict, so the norm is 0 and the gradients are returned unchanged (Q6) -- the default
+        (grad_clip_mode="reference").  The rule it meant to apply is the opt-in grad_clip_mode="global_norm", which runs
+        inside the captured step (api.value_and_grad(grad_clip=), csrc/clip.hip), not here."""
         return grads
 
     def _get_latent_stats(self):
