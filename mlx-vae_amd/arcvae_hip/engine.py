@@ -423,7 +423,7 @@ class Gates:
     HG "the heads' parameter gradients of this step are formed" (1 per step, raised by aux behind heads_wgrad: the
     data-parallel step reduces that 1.58 MB bucket early, on side -- dp.EngineOps.seam_buckets).
     """
-    STRIDE = 8
+    STRIDE = 9                         # P: #1 (inputs ready) + one per BPTT chunk, up to the 8 chunk launches of a persistent sweep
     LONG, SHORT = 16_000_000, 3_000    # polls (~1.5 us each): ~25 s before a gate gives up (a first RCCL collective
                                        # or a peer still capturing its graphs may hold main up for seconds); ~4 ms probe
     P, Q, NS, NA, ERR, PROBE, R, NM, D, H, HG = range(11)

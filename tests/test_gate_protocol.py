@@ -218,7 +218,8 @@ def _replay(ops, streams, steps):
                                  {"ARCVAE_HEADS_EARLY": "1"}])
 @pytest.mark.parametrize("persistent", [False, True])
 @pytest.mark.parametrize("T,L,fractions", [(128, 2, (0.3, 0.6, 0.85, 1.0)), (128, 2, (0.63, 1.0)), (12, 2, (0.63, 1.0)),
-                                           (40, 4, (0.1, 0.2, 0.3, 0.5, 0.7, 0.9, 1.0)), (9, 1, (0.5, 1.0)), (5, 3, (0.3, 0.6, 0.85, 1.0))])
+                                           (40, 4, (0.1, 0.2, 0.3, 0.5, 0.7, 0.9, 1.0)), (9, 1, (0.5, 1.0)), (5, 3, (0.3, 0.6, 0.85, 1.0)),
+                                           (128, 2, (0.1, 0.2, 0.3, 0.4, 0.5, 0.6, 0.7, 1.0))])
 @pytest.mark.parametrize("dp", [False, True])
 @pytest.mark.parametrize("tables_on_main", [False, True])
 def test_gated_backward_never_blocks_and_keeps_its_order(T, L, fractions, persistent, env, dp, tables_on_main, monkeypatch):
