@@ -366,6 +366,30 @@ int arcvae_dec_beam_search(const float* dense_logits, const float* lse, int32_t*
                            float temperature, arcvae_stream_t stream);
 int arcvae_dec_sequence_logprob(const float* dense_logits, const float* lse, const int32_t* tokens, float* out, int B, int T, int V,
                                 int end_token, float temperature, arcvae_stream_t stream);
+/* EXTENSION (no reference counterpart: the reference decodes greedily) -- top-k / nucleus (top-p) truncated sampling over the dense
+ * logits [B*V, V] of arcvae_dec_forward_dense (mode 0); row r = b*V + c holds batch row b's logits after token c.
+ * 1 <= vocab_size <= 256, temperature > 0, top_k >= 0 (0 = all V), 0 < top_p <= 1; anything else (NaN included) is ARCVAE_ERR_ARG.
+ * Scaled logits s_j = fl(x_j * fl(1.0f / temperature)).  Order: token j precedes token i iff s_j > s_i, or s_j == s_i and j < i.
+ * Top-k set K = the first min(top_k, V) tokens of that order.  Masses e_j = expf(s_j - max s), C_i = the fp32 inclusive prefix sum
+ * of e over K in that order (summation order the kernel's), M_K = C_{|K|-1}.  Nucleus set P: position i of K is kept iff
+ * fl(C_i - e_i) < fl(top_p * M_K) (the mass strictly before it is below the threshold); top_p = 1 keeps every position of K with
+ * e_i > 0; position 0 is always kept; n = |P| = the first position that fails (|K| if none), so K and P are prefixes of the order.
+ * arcvae_dec_topkp_rows: the truncated distribution of R table rows (rows[i] = a table-row id, clamped into [0, table_rows); rows
+ *   NULL = rows 0 .. R-1, R <= table_rows): count[i] = n, tokens[i, 0..V) = the row's whole order, cum[i, p] = C_p for p < |K|,
+ *   0 beyond.  It is the inspection point of the walk: both run the same device code and agree bit for bit.
+ * arcvae_dec_sample_chain_topkp: per batch row b from token 0; step t at token c reads row b*V + c, u24 = mix64(mix64(seed ^
+ *   (b << 32)) + t) >> 40 (the generator of arcvae_dec_sample_chain_categorical), theta = fl(fl(u24 * 2^-24) * C_{n-1}), picks
+ *   the first position i < n with C_i > theta (n-1 if none) and writes tokens[b, t] = its token; first_end as
+ *   arcvae_dec_sample_chain (tokens after EOS are still generated).  `seed` is a DEVICE pointer to one 64-bit word, read by the
+ *   kernel: a captured launch serves every seed.  ws: caller-owned device scratch of at least arcvae_dec_topkp_ws_bytes(B, V, top_k)
+ *   bytes (a pre-pass stores every table row's truncated distribution there; the walk reads it).  No atomics: repeated calls are
+ *   bitwise identical.  Rows holding a NaN or inf logit are outside the contract; they still write tokens in [0, V). */
+int arcvae_dec_topkp_rows(const float* dense_logits, long table_rows, const int32_t* rows, long R, int V, float temperature,
+                          int top_k, float top_p, int32_t* count, int32_t* tokens, float* cum, arcvae_stream_t stream);
+int arcvae_dec_topkp_ws_bytes(int B, int V, int top_k, long* bytes);
+int arcvae_dec_sample_chain_topkp(const float* dense_logits, int32_t* tokens, int32_t* first_end, void* ws, long ws_bytes, int B,
+                                  int V, int max_len, int end_token, float temperature, int top_k, float top_p,
+                                  const unsigned long long* seed, arcvae_stream_t stream);
 /* Backward of arcvae_dec_forward_dense: embedding.weight, lstm_layer_l.{Wx,bias}, fc_out.{weight,bias}.
  * ws: dh [2,B*V,H], dG [B*V,4H], dtableD [V,4H], wcpart [V,4H,max(C,1)]. */
 int arcvae_dec_backward_dense(const float* emb, const float* const* Wx, const float* const* bias,

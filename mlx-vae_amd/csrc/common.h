@@ -92,6 +92,14 @@ __device__ __forceinline__ float chain_tanh(float x) {
 }
 #endif
 
+// splitmix64 finaliser: the counter-based generator of the sampling walks (decoder.hip, sample.hip), keyed by (seed, row, step).
+__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
+    x += 0x9e3779b97f4a7c15ull;
+    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
+    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
+    return x ^ (x >> 31);
+}
+
 // Wave-level reductions over 64 lanes.
 __device__ __forceinline__ float wave_sum(float v) {
 #pragma unroll

@@ -351,12 +351,6 @@ __global__ __launch_bounds__(64) void dec_sample_chain_kernel(const int32_t* __r
 // up to four vocabulary entries, the row's cumulative distribution is a wave scan, the uniform number of step t comes from a
 // counter-based generator keyed by (seed, row, t) (splitmix64 finaliser: reproducible for a seed whatever the launch shape), and the
 // next token is the first entry whose cumulative mass exceeds u * total.
-__device__ __forceinline__ unsigned long long mix64(unsigned long long x) {
-    x += 0x9e3779b97f4a7c15ull;
-    x = (x ^ (x >> 30)) * 0xbf58476d1ce4e5b9ull;
-    x = (x ^ (x >> 27)) * 0x94d049bb133111ebull;
-    return x ^ (x >> 31);
-}
 __global__ __launch_bounds__(256) void dec_sample_categorical_kernel(const float* __restrict__ logits, int32_t* tokens,
                                                                     int32_t* first_end, int B, int V, int max_len,
                                                                     int end_token, float inv_temp, unsigned long long seed) {

@@ -1,0 +1,228 @@
+// Top-k / nucleus (top-p) truncated sampling over the dense decoder table -- an EXTENSION with no reference behaviour to match
+// (the reference's sampler is the greedy walk, models/decoder_sampling.py:48-128).  Contract: include/arcvae_hip.h, restated in
+// NumPy by tests/topkp_ref.py.
+//
+// The decoder is stateless per step: row b*V + c of the dense logits (arcvae_dec_forward_dense, mode 0) is batch
+// row b's next-token distribution after token c.  One device function, topkp_row, truncates a row: one wave, a lane holds the
+// four entries j = 4*lane + e, exactly as the categorical walk (decoder.hip).
+//   1. s_j = fl(x_j * inv_temp); key_j = (order-preserving 32-bit image of s_j) << 8 | (255 - j): unique, and descending key
+//      order is the contract's order (s descending, then token ascending; -0 is folded into +0 first, as s compares them equal).
+//   2. a bitonic sort of the 256 keys, descending, across the wave: position p = 4*lane + e; partners at distance 1 and 2 are
+//      in the lane, the others one __shfl_xor away.  Padding entries (j >= V) hold key 0 and sort behind every real one.
+//   3. e_p = expf(s_p - s_0) for p < |K| = min(k, V), 0 beyond; C = inclusive scan in sorted order (in-lane, then across lanes).
+//   4. n = the first position p >= 1 of K that fails the nucleus test fl(C_p - e_p) < fl(p * M_K) (|K| if none).
+// Placement: a pre-pass truncates all B*V rows once, in parallel (topkp_rows_kernel<true>: count, the |K| cumulative masses and
+// tokens of each row into the caller's workspace), and the walk (one wave per batch row) only reads those lists.  Truncating
+// inside the walk instead, for the B * max_len rows it visits, was measured at 0.42 / 0.67 ms per bs-1024 batch (max_length
+// 80 / 128, V 80) against 0.23 / 0.27 ms for pre-pass + walk: one wave per SIMD has nothing to hide the sort's latency
+// (DESIGN.md section 10).  The pre-pass and the
+// materialising entry point run the same topkp_row, so the walk's decisions are those of the inspected rows, bit for bit.
+#include "common.h"
+
+namespace {
+
+constexpr int TOPKP_MAX_V = 256;
+
+__device__ __forceinline__ unsigned long long topkp_max(unsigned long long a, unsigned long long b) { return a > b ? a : b; }
+__device__ __forceinline__ unsigned long long topkp_min(unsigned long long a, unsigned long long b) { return a < b ? a : b; }
+
+// element e (wave-uniform) of a lane's four values, without a dynamically indexed array (which would live in scratch)
+template <typename T>
+__device__ __forceinline__ T topkp_pick4(const T (&v)[4], int e) {
+    return e == 0 ? v[0] : (e == 1 ? v[1] : (e == 2 ? v[2] : v[3]));
+}
+
+// Position p = 4*lane + e of the wave's 256 keys: descending bitonic sort (blocks of size k alternate direction; the last
+// stage, k = 256, is one descending block).  Keys are unique, so min / max pick one element of each pair.
+__device__ __forceinline__ void topkp_sort(unsigned long long (&key)[4], int lane) {
+#pragma unroll
+    for (int k = 2; k <= TOPKP_MAX_V; k <<= 1) {
+#pragma unroll
+        for (int j = k >> 1; j > 0; j >>= 1) {
+            unsigned long long other[4];
+            if (j >= 4) {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) other[e] = __shfl_xor(key[e], j >> 2, 64);
+            } else {
+#pragma unroll
+                for (int e = 0; e < 4; ++e) other[e] = key[e ^ j];
+            }
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                const int p = 4 * lane + e;
+                const bool desc = (p & k) == 0, lower = (p & j) == 0;
+                key[e] = (lower == desc) ? topkp_max(key[e], other[e]) : topkp_min(key[e], other[e]);
+            }
+        }
+    }
+}
+
+// The truncated distribution of one table row (wave-wide; every output is per lane for positions 4*lane + e, n and c_last are
+// wave-uniform): tok = the whole order (positions < V), cum = C (positions < |K|; 0 beyond), n = |P|.
+__device__ __forceinline__ void topkp_row(const float* __restrict__ row, int V, float inv_temp, int K, float top_p, int lane,
+                                          int (&tok)[4], float (&cum)[4], int& n) {
+    unsigned long long key[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int j = 4 * lane + e;
+        key[e] = 0ull;
+        if (j < V) {
+            float s = row[j] * inv_temp;
+            if (s == 0.f) s = 0.f;                       // -0 == +0: one key, the tie goes to the token index
+            const unsigned u = __float_as_uint(s);
+            const unsigned k32 = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+            key[e] = ((unsigned long long)k32 << 8) | (unsigned long long)(255 - j);
+        }
+    }
+    topkp_sort(key, lane);
+    float s[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        tok[e] = 255 - (int)(key[e] & 255ull);
+        const unsigned k32 = (unsigned)(key[e] >> 8);
+        s[e] = __uint_as_float((k32 & 0x80000000u) ? (k32 & 0x7fffffffu) : ~k32);
+    }
+    const float m = __shfl(s[0], 0, 64);                  // position 0: the row's largest s
+    float ev[4], c[4], run = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        ev[e] = 4 * lane + e < K ? expf(s[e] - m) : 0.f;
+        run += ev[e];
+        c[e] = run;
+    }
+    float incl = run;                                     // inclusive scan of the lanes' totals
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    float before = __shfl_up(incl, 1, 64);
+    if (lane == 0) before = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) cum[e] = 4 * lane + e < K ? before + c[e] : 0.f;
+    const float mk = __shfl(topkp_pick4(cum, (K - 1) & 3), (K - 1) >> 2, 64);   // M_K = C_{|K|-1}
+    const float thr = top_p * mk;
+    int fail = TOPKP_MAX_V;
+#pragma unroll
+    for (int e = 3; e >= 0; --e) {
+        const int p = 4 * lane + e;
+        const bool keep = top_p >= 1.f ? ev[e] > 0.f : cum[e] - ev[e] < thr;
+        if (p >= 1 && p < K && !keep) fail = p;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) fail = min(fail, __shfl_xor(fail, o, 64));
+    n = min(fail, K);
+}
+
+// ---- materialise: one wave per listed table row.  PREPASS (the walk's lists): positions < S = |K| only, cum [R, S] f32 and
+// tok [R, S] u8; otherwise (the inspection entry point) the whole order as int32 and cum over V columns ------------------------
+template <bool PREPASS>
+__global__ __launch_bounds__(256) void topkp_rows_kernel(const float* __restrict__ logits, long table_rows,
+                                                         const int32_t* __restrict__ rows, long R, int V, float inv_temp, int K,
+                                                         float top_p, int32_t* count, void* tokens, float* cum) {
+    const int lane = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= R) return;                                   // wave-uniform
+    const long r = rows ? min(max((long)rows[i], 0L), table_rows - 1) : i;
+    int tk[4], n;
+    float cm[4];
+    topkp_row(logits + r * V, V, inv_temp, K, top_p, lane, tk, cm, n);
+    const int S = PREPASS ? K : V;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int p = 4 * lane + e;
+        if (p < S) {
+            if (PREPASS) ((uint8_t*)tokens)[i * S + p] = (uint8_t)tk[e];
+            else ((int32_t*)tokens)[i * S + p] = tk[e];
+            cum[i * S + p] = cm[e];
+        }
+    }
+    if (lane == 0) count[i] = n;
+}
+
+// ---- the walk over the pre-pass lists: one wave per batch row, the seed read from device memory (one captured graph serves
+// every seed).  A step issues its row's count and lists together: one dependent round of loads per step -------------------------
+__global__ __launch_bounds__(256) void topkp_walk_kernel(const int32_t* __restrict__ count, const float* __restrict__ cum,
+                                                         const uint8_t* __restrict__ tok, int32_t* tokens, int32_t* first_end,
+                                                         int B, int V, int S, int max_len, int end_token,
+                                                         const unsigned long long* __restrict__ seed_ptr) {
+    const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (b >= B) return;                                   // wave-uniform
+    const unsigned long long seed = *seed_ptr;
+    const unsigned long long key0 = mix64(seed ^ ((unsigned long long)b << 32));
+    int cur = 0, fe = max_len;
+    for (int t = 0; t < max_len; ++t) {
+        const long r = (long)b * V + cur;
+        float cm[4];
+        int tk[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            const int p = 4 * lane + e;
+            cm[e] = p < S ? cum[r * S + p] : 0.f;
+            tk[e] = p < S ? (int)tok[r * S + p] : 0;
+        }
+        const int n = min(max(count[r], 1), S);
+        const float c_last = __shfl(topkp_pick4(cm, (n - 1) & 3), (n - 1) >> 2, 64);
+        const unsigned long long rnd = mix64(key0 + (unsigned long long)t);
+        const float theta = (float)(rnd >> 40) * (1.0f / 16777216.0f) * c_last;   // 24 uniform bits in [0, 1), times C_{n-1}
+        int pick = n - 1;                                 // (no C_i above theta: the last kept position)
+#pragma unroll
+        for (int e = 3; e >= 0; --e)
+            if (4 * lane + e < n && cm[e] > theta) pick = 4 * lane + e;
+#pragma unroll
+        for (int o = 32; o > 0; o >>= 1) pick = min(pick, __shfl_xor(pick, o, 64));
+        cur = min(__shfl(topkp_pick4(tk, pick & 3), pick >> 2, 64), V - 1);
+        if (lane == 0) tokens[(long)b * max_len + t] = cur;
+        if (cur == end_token && fe == max_len) fe = t;
+    }
+    if (lane == 0) first_end[b] = fe;
+}
+
+bool topkp_args_ok(int V, float temperature, int top_k, float top_p) {
+    return V >= 1 && V <= TOPKP_MAX_V && temperature > 0.f && top_k >= 0 && top_p > 0.f && top_p <= 1.f;   // (NaN fails)
+}
+
+int topkp_set_size(int V, int top_k) { return top_k == 0 ? V : min(top_k, V); }
+
+// pre-pass lists of B*V rows: count [R] i32 | cum [R, S] f32 | tok [R, S] u8, S = |K|
+long topkp_ws_bytes(int B, int V, int top_k) {
+    const long R = (long)B * V, S = topkp_set_size(V, top_k);
+    return R * 4 + R * S * 4 + R * S;
+}
+
+}  // namespace
+
+extern "C" int arcvae_dec_topkp_rows(const float* dense_logits, long table_rows, const int32_t* rows, long R, int V,
+                                     float temperature, int top_k, float top_p, int32_t* count, int32_t* tokens, float* cum,
+                                     hipStream_t stream) {
+    if (!dense_logits || !count || !tokens || !cum || table_rows <= 0 || R <= 0 || !topkp_args_ok(V, temperature, top_k, top_p))
+        return ARCVAE_ERR_ARG;
+    if ((!rows && R > table_rows) || (R + 3) / 4 > 0x7fffffffL) return ARCVAE_ERR_ARG;
+    hipLaunchKernelGGL(topkp_rows_kernel<false>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, stream, dense_logits, table_rows, rows,
+                       R, V, 1.0f / temperature, topkp_set_size(V, top_k), top_p, count, (void*)tokens, cum);
+    return arcvae_launch_status();
+}
+
+extern "C" int arcvae_dec_topkp_ws_bytes(int B, int V, int top_k, long* bytes) {
+    if (!bytes || B <= 0 || V < 1 || V > TOPKP_MAX_V || top_k < 0) return ARCVAE_ERR_ARG;
+    *bytes = topkp_ws_bytes(B, V, top_k);
+    return ARCVAE_OK;
+}
+
+extern "C" int arcvae_dec_sample_chain_topkp(const float* dense_logits, int32_t* tokens, int32_t* first_end, void* ws, long ws_bytes,
+                                             int B, int V, int max_len, int end_token, float temperature, int top_k, float top_p,
+                                             const unsigned long long* seed, hipStream_t stream) {
+    if (!dense_logits || !tokens || !first_end || !ws || !seed || B <= 0 || max_len <= 0 ||
+        !topkp_args_ok(V, temperature, top_k, top_p))
+        return ARCVAE_ERR_ARG;
+    if (ws_bytes < topkp_ws_bytes(B, V, top_k) || ((long)B * V + 3) / 4 > 0x7fffffffL) return ARCVAE_ERR_ARG;
+    const long R = (long)B * V, S = topkp_set_size(V, top_k);
+    int32_t* count = (int32_t*)ws;
+    float* cum = (float*)(count + R);
+    uint8_t* tok = (uint8_t*)(cum + R * S);
+    hipLaunchKernelGGL(topkp_rows_kernel<true>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, stream, dense_logits, R,
+                       (const int32_t*)nullptr, R, V, 1.0f / temperature, (int)S, top_p, count, (void*)tok, cum);
+    hipLaunchKernelGGL(topkp_walk_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, stream, count, cum, tok, tokens, first_end, B, V,
+                       (int)S, max_len, end_token, seed);
+    return arcvae_launch_status();
+}

@@ -6,7 +6,8 @@ early stopping the output is cut where every row has emitted EOS.  One dense dec
 (B*V rows) + one table walk replaces the reference's max_length dependent steps and its per-step
 host sync; `load_from_decoder` is an explicit extension to sample from trained weights, and `sample=True` the true categorical
 sampling the reference marks TODO (decoder_sampling.py:115-116): an extension with no reference behaviour to match.  So is
-`generate_beam` (beam search with scores, csrc/beam.hip); `decoder.sequence_log_prob` scores given sequences."""
+`generate_beam` (beam search with scores, csrc/beam.hip); `decoder.sequence_log_prob` scores given sequences; and
+`sample=True` with `top_k` / `top_p` (truncated sampling, csrc/sample.hip)."""
 from __future__ import annotations
 
 import torch
@@ -38,11 +39,18 @@ class MLXAutoregressiveDecoderSampling:
 
     def generate_with_temperature(self, z, conditions, max_length: int = 80, temperature: float = 1.0,
                                   early_stopping: bool = True, use_graph: bool = True, *, sample: bool = False,
-                                  seed: int = 0) -> torch.Tensor:
+                                  seed: int = 0, top_k=None, top_p=None) -> torch.Tensor:
         """[B, t_stop] int32 tokens (models/decoder_sampling.py:48-128).  z is accepted and unused (Q2).
         sample=True (keyword-only extension; the default reproduces the reference's greedy "temperature sampling", Q9): every token is
         DRAWN from softmax(logits / temperature) -- what decoder_sampling.py:115-116 leaves as a TODO -- with a counter-based
-        generator keyed by (seed, row, step): the same seed returns the same molecules."""
+        generator keyed by (seed, row, step): the same seed returns the same molecules.
+        top_k / top_p (keyword-only extension, with sample=True): draw from the truncated distribution instead -- the top_k most
+        likely tokens (ties to the lower token), then the smallest prefix of them holding top_p of their renormalised mass
+        (include/arcvae_hip.h arcvae_dec_sample_chain_topkp).  None = no truncation of that kind; both None = the categorical path."""
+        if top_k is not None or top_p is not None:
+            if not sample:
+                raise ValueError("top_k / top_p need sample=True")
+            return self._generate_topkp(conditions, max_length, temperature, early_stopping, use_graph, int(seed), top_k, top_p)
         if sample:
             return self._generate_categorical(conditions, max_length, temperature, early_stopping, int(seed))
         dec = self.decoder
@@ -101,6 +109,63 @@ class MLXAutoregressiveDecoderSampling:
              dec.end_token, float(temperature), C.c_ulonglong(seed & 0xFFFFFFFFFFFFFFFF), stream_ptr())
         if early_stopping:
             tokens = tokens[:, :min(int(first_end.max().item()) + 1, max_length)]
+        return tokens.clone()
+
+    def _generate_topkp(self, conditions, max_length: int, temperature: float, early_stopping: bool, use_graph: bool, seed: int,
+                        top_k, top_p) -> torch.Tensor:
+        """One dense decoder pass (mode 0: raw logits of all B*V (row, token) pairs), then arcvae_dec_sample_chain_topkp: a pre-pass
+        truncates every table row once, and a wave per row walks start token -> drawn token -> ... through those lists.  The seed is
+        read by the kernel from a device word written before the launch, so the pass is captured once per (B, max_length,
+        temperature, top_k, top_p) and replayed for every seed; use_graph=False launches the same kernels eagerly."""
+        import ctypes as C
+        if not temperature > 0.0:
+            raise ValueError("temperature must be > 0 for top-k / top-p sampling")
+        k = 0 if top_k is None else int(top_k)
+        if top_k is not None and k < 1:
+            raise ValueError("top_k must be >= 1")
+        p = 1.0 if top_p is None else float(top_p)
+        if not 0.0 < p <= 1.0 or not 0.0 < float(C.c_float(p).value) <= 1.0:
+            raise ValueError("top_p must lie in (0, 1]")
+        dec = self.decoder
+        if dec.vocab_size > 256:
+            raise ValueError("top-k / top-p sampling needs vocab_size <= 256")
+        dev = dec.store.device
+        cond = as_f32(conditions, dev)
+        B = cond.shape[0]
+        ws = dec.workspace(B, max_length)
+        ws.cond.copy_(cond.reshape(B, dec.num_conditions))
+        key = ("topkp", B, max_length, float(temperature), k, p)
+        if key not in self._graphs:
+            nbytes = C.c_long(0)
+            call("arcvae_dec_topkp_ws_bytes", B, dec.vocab_size, k, C.byref(nbytes))
+            self._graphs[key] = dict(tokens=torch.zeros(B, max_length, dtype=torch.int32, device=dev),
+                                     first_end=torch.zeros(B, dtype=torch.int32, device=dev),
+                                     seed=torch.zeros(1, dtype=torch.int64, device=dev),
+                                     scratch=torch.empty(nbytes.value, dtype=torch.uint8, device=dev), graph=None)
+        st = self._graphs[key]
+        s64 = seed & 0xFFFFFFFFFFFFFFFF
+        st["seed"].fill_(s64 - (1 << 64) if s64 >= 1 << 63 else s64)       # the 64-bit word the kernel reads
+
+        def enqueue():
+            E.decoder_forward_dense(dec.store, ws, dec.dims, mode=0, keep_gpre=False, alone=True)
+            call("arcvae_dec_sample_chain_topkp", ptr(ws.logits), ptr(st["tokens"]), ptr(st["first_end"]), ptr(st["scratch"]),
+                 st["scratch"].numel(), B, dec.vocab_size, max_length, dec.end_token, float(temperature), k, p, ptr(st["seed"]),
+                 stream_ptr())
+
+        if not use_graph:
+            enqueue()
+        elif st["graph"] is None:
+            enqueue()  # first call runs eagerly, then the decode pass is captured for replay
+            torch.cuda.synchronize()
+            g = torch.cuda.CUDAGraph()
+            with torch.cuda.graph(g):
+                enqueue()
+            st["graph"] = g
+        else:
+            st["graph"].replay()
+        tokens = st["tokens"]
+        if early_stopping:
+            tokens = tokens[:, :min(int(st["first_end"].max().item()) + 1, max_length)]
         return tokens.clone()
 
     def generate_beam(self, z, conditions, max_length: int = 80, beam_width: int = 4, temperature: float = 1.0,

@@ -32,15 +32,19 @@ class ARCVAE:
         return logits, mu, logvar, z
 
     def generate(self, batch_size: int, conditions, max_length: int = 80, temperature: float = 1.0, *, sample: bool = False,
-                 seed: int = 0, beam_width: Optional[int] = None) -> torch.Tensor:
+                 seed: int = 0, beam_width: Optional[int] = None, top_k: Optional[int] = None,
+                 top_p: Optional[float] = None) -> torch.Tensor:
         """models/vae.py:101-131: z ~ N(0,I) (unused downstream, Q2) -> greedy sampler.  sample / seed (keyword-only extension):
         true categorical sampling instead of the reference's argmax, see MLXAutoregressiveDecoderSampling.  beam_width
-        (keyword-only extension): the best hypothesis of a beam search of that width, [B, L] (generate_beam, early stopping)."""
+        (keyword-only extension): the best hypothesis of a beam search of that width, [B, L] (generate_beam, early stopping).
+        top_k / top_p (keyword-only extension, with sample=True): top-k / nucleus truncated sampling."""
         dev = self.decoder_sampling.decoder.store.device
         z = torch.randn(batch_size, self.latent_dim, device=dev)
         if beam_width is not None:
             if sample:
                 raise ValueError("beam_width and sample=True are exclusive")
+            if top_k is not None or top_p is not None:
+                raise ValueError("top_k / top_p do not apply to beam search")
             tokens, _ = self.decoder_sampling.generate_beam(z, conditions, max_length=max_length, beam_width=beam_width,
                                                             temperature=temperature)
             best = tokens[:, 0, :]
@@ -48,7 +52,8 @@ class ARCVAE:
             length = torch.where(ended.any(1), ended.int().argmax(1) + 1, best.shape[1])
             return best[:, :int(length.max().item())].contiguous()
         return self.decoder_sampling.generate_with_temperature(z, conditions, max_length=max_length,
-                                                               temperature=temperature, sample=sample, seed=seed)
+                                                               temperature=temperature, sample=sample, seed=seed,
+                                                               top_k=top_k, top_p=top_p)
 
     def parameters(self):
         return {"encoder": self.encoder.parameters(), "decoder": self.decoder.parameters(),
