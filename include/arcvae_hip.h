@@ -486,6 +486,25 @@ int arcvae_adam_update_finalize_clipped(float* params, const float* grads, float
                                         int Z, int T, const float* partials, long n_partials, double max_norm,
                                         arcvae_stream_t stream);
 
+/* ---- learning-rate schedules: the rate as a device word (an extension: the reference trains at one rate, trainer.py:75-76) ----
+ * The four update forms above with the learning rate READ FROM DEVICE MEMORY at execution time (lr_dev: one fp32 word), so that
+ * a launch captured in a hipGraph serves every rate.  rowloss non-null selects the finalize part (arcvae_adam_update_finalize:
+ * stats, scalars, B, Z, T required), partials non-null the clip part (arcvae_adam_update_clipped: scalars required); neither,
+ * either or both.  Same expressions, order, grid and float4 / scalar-tail split as the by-value forms: with *lr_dev == (float)lr
+ * the results are bitwise theirs.  When `scalars` is non-null, block 0 also writes scalars[13] = *lr_dev, the rate this launch
+ * applied.  A word that is negative, infinite or NaN updates nothing (params, m, v untouched; scalars[13] shows the word; the
+ * finalize and clip scalars are still written -- the same split as a guard word, but not poisoned).  A zero word is a valid
+ * rate: m and v advance, params do not move.
+ * ARCVAE_ERR_ARG before any launch: null params / grads / m / v / lr_dev, n <= 0; a finalize part with null stats or scalars
+ * or non-positive B, Z or T; a clip part with null scalars, n_partials outside [1, 4096], max_norm <= 0 or not finite. */
+int arcvae_adam_step(float* params, const float* grads, float* m, float* v, long n,
+                     const float* lr_dev,            /* DEVICE, one fp32 word, read by the kernel */
+                     double beta1, double beta2, double eps,
+                     const unsigned* guard_a, const unsigned* guard_b,
+                     const float* rowloss, int B, float* stats, float* scalars, int Z, int T,  /* finalize part: rowloss NULL = none */
+                     const float* partials, long n_partials, double max_norm,                   /* clip part: partials NULL = none   */
+                     arcvae_stream_t stream);
+
 /* ---- small helpers ---------------------------------------------------------------------------------- */
 int arcvae_colsum_accum(const float* X, int rows, int cols, int ld, float* out, float scale,
                         arcvae_stream_t stream);

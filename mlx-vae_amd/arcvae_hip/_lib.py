@@ -119,6 +119,7 @@ SIGNATURES = {
     "arcvae_adam_update_clipped": [_vp, _vp, _vp, _vp, _l, _d, _d, _d, _d, _vp, _vp, _vp, _l, _d, _vp, _vp],
     "arcvae_adam_update_finalize_clipped": [_vp, _vp, _vp, _vp, _l, _d, _d, _d, _d, _vp, _vp, _vp, _i, _vp, _vp, _i, _i,
                                             _vp, _l, _d, _vp],
+    "arcvae_adam_step": [_vp, _vp, _vp, _vp, _l, _vp, _d, _d, _d, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _l, _d, _vp],
 }
 
 LONG_RESULTS = {"arcvae_enc_lstm_bwd_rs_part_floats"}      # size queries returning `long`; everything else returns an int code

@@ -62,7 +62,8 @@ def draw_eps(B: int, Z: int, device, generator: Optional[torch.Generator] = None
     return torch.randn(B, Z, device=device, dtype=torch.float32, generator=generator)
 
 
-def _as_dict(eng: StepEngine, ws, clone: bool, status: bool = False, clip: bool = False) -> Dict[str, torch.Tensor]:
+def _as_dict(eng: StepEngine, ws, clone: bool, status: bool = False, clip: bool = False,
+             rate: bool = False) -> Dict[str, torch.Tensor]:
     sc = ws.scalars.clone()  # 16 floats: always detach from the static buffer the next call overwrites
     out = {k: sc[i] for i, k in enumerate(SCALAR_KEYS)}
     if status:   # [total_loss, step status]: ONE D2H read gives the trainer the loss and "stream order was lost"
@@ -70,6 +71,8 @@ def _as_dict(eng: StepEngine, ws, clone: bool, status: bool = False, clip: bool 
     if clip:     # the global-norm clip: pre-clip norm and applied scale; [loss, status, norm] for the same single read
         out["grad_norm"], out["clip_scale"] = sc[11], sc[12]
         out["loss_status_norm"] = torch.stack((sc[0], sc[15], sc[11]))
+    if rate:     # device-rate mode: the rate the encoder's update applied
+        out["lr"] = sc[13]
     for k in ("mu", "logvar", "z"):
         t = getattr(ws, k)
         out[k] = t.clone() if clone else t
@@ -98,15 +101,21 @@ def loss_forward(encoder, decoder, x, conditions, eps=None, coins=None, teacher_
 
 
 def value_and_grad(encoder, decoder, x, conditions, eps=None, coins=None, teacher_forcing_ratio: float = 0.9,
-                   lr: Optional[float] = None, predictor=None, grad_clip: Optional[float] = None, **hyper):
+                   lr: Optional[float] = None, predictor=None, grad_clip: Optional[float] = None, lr_device: bool = False,
+                   **hyper):
     """(loss dict, (encoder grad tree, decoder grad tree)); with `lr` given the two Adam updates are applied
     in the same captured step (trainer.py:305-333).  With a predictor (hyper must include lambda_prop, ValueError
     otherwise): (loss dict, (encoder, decoder, predictor grad trees)) and three Adam updates.
     grad_clip (opt-in, needs lr): the updates apply the global-norm clip with max_norm = grad_clip --
     the reference's intended `_clip_gradients` rule over every gradient of the step.  The returned gradient trees stay the
-    UNCLIPPED ones; the loss dict also holds "grad_norm" (pre-clip), "clip_scale" and "loss_status_norm"."""
+    UNCLIPPED ones; the loss dict also holds "grad_norm" (pre-clip), "clip_scale" and "loss_status_norm".
+    lr_device (opt-in, needs lr): lr (finite, >= 0) travels as a device word, so that a rate that changes
+    from step to step -- a warmup or decay schedule -- replays the same captured step; the loss dict also holds "lr", the rate
+    the update applied."""
     if grad_clip is not None and lr is None:
         raise ValueError("grad_clip needs lr: without an update there is nothing to clip")
+    if lr_device and lr is None:
+        raise ValueError("lr_device needs lr: without an update no rate is applied")
     from .engine import check_clip_norm
     clip = check_clip_norm(grad_clip)
     eng = engine_for(encoder, decoder, predictor)
@@ -120,11 +129,13 @@ def value_and_grad(encoder, decoder, x, conditions, eps=None, coins=None, teache
         if lr is None:
             raise ValueError("the data-parallel step applies both Adam updates: pass lr")
         x, conditions = _dev_batch(eng, x, conditions)
-        ws = dp.train_step(x, conditions, _local_eps(dp, eps, B), coins, lr, clip_norm=clip, **hyper)
-        return _as_dict(eng, ws, clone=False, status=True, clip=clip is not None), (encoder.gradients(), decoder.gradients())
-    eng.train_step(x, conditions, eps, coins, lr=lr if lr is not None else 0.0, update=lr is not None, clip_norm=clip, **hyper)
+        ws = dp.train_step(x, conditions, _local_eps(dp, eps, B), coins, lr, clip_norm=clip, lr_device=lr_device,
+                           **hyper)
+        return _as_dict(eng, ws, clone=False, status=True, clip=clip is not None, rate=lr_device), (encoder.gradients(), decoder.gradients())
+    eng.train_step(x, conditions, eps, coins, lr=lr if lr is not None else 0.0, update=lr is not None, clip_norm=clip,
+                   lr_device=lr_device, **hyper)
     ws = eng.workspace(B, T, train=True)
-    out = _as_dict(eng, ws, clone=False, status=True, clip=clip is not None)
+    out = _as_dict(eng, ws, clone=False, status=True, clip=clip is not None, rate=lr_device)
     if predictor is not None:
         return out, (encoder.gradients(), decoder.gradients(), predictor.gradients())
     return out, (encoder.gradients(), decoder.gradients())

@@ -175,12 +175,14 @@ class EngineOps:
     late bucket and applies both clipped updates.  Late and event forms: both sums of squares in the finish.
     """
 
-    def __init__(self, engine, ws, lr: float, global_rows: int, use_graph: bool = True,
+    def __init__(self, engine, ws, lr, global_rows: int, use_graph: bool = True,
                  group: Optional[dist.ProcessGroup] = None, clip: Optional[float] = None):
         """group: the communicator of the DataParallelStep this ops object will be driven by (None = the default group).  The
         two collectives issued HERE -- the warm-up and the agreement on the gated / event form -- run on it: with a subgroup,
         ranks outside it never construct an EngineOps, and a collective on the default group would hang."""
-        self.eng, self.ws, self.lr = engine, ws, float(lr)
+        from .engine import DeviceRate
+        self.eng, self.ws = engine, ws
+        self.lr = lr if isinstance(lr, DeviceRate) else float(lr)   # (device-rate mode: the workspace's rate word)
         self.group = group
         self.global_rows = int(global_rows)
         self.clip = clip                 # global-norm clip's max_norm, or None
@@ -332,7 +334,7 @@ class EngineOps:
                 return
             if not self.early:                                        # (early form: the decoder's update rode on side)
                 adam_update(eng.dec, self.lr, guards=(ga, gb))
-            adam_update(eng.enc, self.lr, guards=(ga, gb))
+            adam_update(eng.enc, self.lr, guards=(ga, gb), scalars=ws.scalars)
         self.run("dp_finish" if self.early else "dp_finish_late", fn, torch.cuda.current_stream())
 
     # ---- StepOps ----------------------------------------------------------------------------------------
@@ -501,24 +503,29 @@ class EngineDataParallel:
     def _load(self, ws, x, cond, eps, coins, lo, hi):
         self.eng.load_inputs(ws, x[lo:hi], cond[lo:hi], None if eps is None else eps[lo:hi], coins)
 
-    def train_step(self, x, cond, eps, coins, lr: float, clip_norm: Optional[float] = None, **hyper):
+    def train_step(self, x, cond, eps, coins, lr: float, clip_norm: Optional[float] = None, lr_device: bool = False,
+                   **hyper):
         """Loss, gradients and both Adam updates for the GLOBAL batch (x, cond, eps: all rows, identical on every rank;
         eps may also be this rank's own draw of the right shape: no loss value depends on it, Q2).  Returns the local
         workspace: ws.scalars are the global batch's loss scalars.  clip_norm: the global-norm clip of the global gradients
-        (EngineOps; ws.scalars[11] / [12] = its norm and scale, the same on every rank)."""
-        from .engine import check_clip_norm
+        (EngineOps; ws.scalars[11] / [12] = its norm and scale, the same on every rank).  lr_device: the rate as a device word
+        (StepEngine.train_step); every rank writes its own word from the same host value -- no collective -- and one driver
+        serves every rate (ws.scalars[13] = the applied rate)."""
+        from .engine import check_clip_norm, lr_key
         clip = check_clip_norm(clip_norm)
         eng = self.eng
         n, T = int(x.shape[0]), int(x.shape[1])
         lo, hi, replicated = self.bounds(n)
         if replicated:       # fewer rows than ranks: the single-process step on every rank, then rank 0's state everywhere
-            eng.train_step(x, cond, eps, coins, lr=lr, update=True, clip_norm=clip, **hyper)
+            eng.train_step(x, cond, eps, coins, lr=lr, update=True, clip_norm=clip, lr_device=lr_device, **hyper)
             self._broadcast_state()
             return eng.workspace(n, T, train=True)
         ws = eng.workspace(hi - lo, T, train=True)
         eng.set_hyper(ws, **hyper)
         self._load(ws, x, cond, eps, coins, lo, hi)
-        key = (hi - lo, T, n, float(lr), float(eng.hyper_host["free_bits"]))
+        if lr_device:
+            lr = eng.set_rate(ws, lr)        # beside the input copies: between two steps in main's stream order
+        key = (hi - lo, T, n, lr_key(lr), float(eng.hyper_host["free_bits"]))
         if clip is not None:
             key += (clip,)
         drv = self._drivers.get(key)

@@ -60,6 +60,22 @@ class ModelDims:
             raise ValueError("vocab_size must be in [2, 255] (the vocabulary-dense decoder's per-row V x V histogram lives in LDS)")
 
 
+class DeviceRate:
+    """The learning rate of a step in device-rate mode (lr_device=True): not a value but the workspace's
+    fp32 device word, which every update launch reads when it EXECUTES (arcvae_adam_step).  StepEngine.set_rate writes it."""
+    __slots__ = ("word",)
+
+    def __init__(self, word: torch.Tensor):
+        self.word = word
+
+
+LR_DEVICE = "lr_device"      # what a capture key carries in place of float(lr): one captured set serves every rate
+
+
+def lr_key(lr):
+    return LR_DEVICE if isinstance(lr, DeviceRate) else float(lr)
+
+
 class Workspace:
     """Static device buffers for one (B, T) shape."""
 
@@ -80,6 +96,8 @@ class Workspace:
         self._hyper_vals = None
         self.eps = torch.zeros(B, Z, **f32)
         self.hyper = torch.zeros(8, **f32)
+        self.rate = DeviceRate(torch.zeros(1, **f32))   # the learning-rate word of device-rate steps (StepEngine.set_rate)
+        self._rate_val = None
         # encoder forward
         self.table0 = torch.empty(V, G, **f32)
         self.hseq = torch.empty(L, T, B, H, **f32)
@@ -908,10 +926,27 @@ def _encoder_backward_gated_fused(plan: EncoderBackwardPlan, ws: Workspace, aux,
     run("aux0", aux_seg, aux)
 
 
-def adam_update(store: ParamStore, lr: float, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8,
-                guards=NO_GUARDS) -> None:
+def adam_step(store: ParamStore, rate: DeviceRate, guards=NO_GUARDS, scalars: Optional[torch.Tensor] = None,
+              fin=None, clip=None) -> None:
+    """Any update form with the rate read from the device word (arcvae_adam_step).  fin: None or (ws, Z) -- the loss finalize
+    in block 0; clip: None or (ws, max_norm) -- the global-norm clip; scalars (required by both): [13] = the applied rate."""
+    null = C.c_void_p(0)
+    f = (ptr(fin[0].rowloss), fin[0].B, ptr(fin[0].stats), ptr(scalars), fin[1], fin[0].T) if fin is not None else \
+        (null, 0, null, ptr(scalars), 0, 0)
+    c = (ptr(clip[0].clip_part), C.c_long(clip[0].clip_part.numel()), float(clip[1])) if clip is not None else \
+        (null, C.c_long(0), 0.0)
+    call("arcvae_adam_step", ptr(store.flat), ptr(store.grad), ptr(store.adam_m), ptr(store.adam_v),
+         C.c_long(store.numel_padded), ptr(rate.word), 0.9, 0.999, 1e-8, guards[0], guards[1], *f, *c, stream_ptr())
+
+
+def adam_update(store: ParamStore, lr, b1: float = 0.9, b2: float = 0.999, eps: float = 1e-8,
+                guards=NO_GUARDS, scalars: Optional[torch.Tensor] = None) -> None:
     """trainer.py:320,324 -> MLX optim.Adam (no bias correction, Q7) over the module's flat buffer.
-    guards: two device error words (StepEngine.guards); the kernel skips the update when either is non-zero."""
+    guards: two device error words (StepEngine.guards); the kernel skips the update when either is non-zero.
+    lr: a float, or a DeviceRate (then `scalars`, optional, receives the applied rate in [13])."""
+    if isinstance(lr, DeviceRate):
+        adam_step(store, lr, guards, scalars)
+        return
     call("arcvae_adam_update", ptr(store.flat), ptr(store.grad), ptr(store.adam_m), ptr(store.adam_v),
          C.c_long(store.numel_padded), float(lr), float(b1), float(b2), float(eps), guards[0], guards[1], stream_ptr())
 
@@ -934,10 +969,15 @@ def grad_sumsq(store: ParamStore, ws: Workspace, which: str) -> None:
          C.c_long(cnt), stream_ptr())
 
 
-def adam_update_clipped(store: ParamStore, lr: float, ws: Workspace, clip_norm: float, guards=NO_GUARDS,
+def adam_update_clipped(store: ParamStore, lr, ws: Workspace, clip_norm: float, guards=NO_GUARDS,
                         scalars: Optional[torch.Tensor] = None) -> None:
     """Global-norm clip, step 2: adam_update on g * scale, the scale derived in every block from ALL partials of ws.clip_part
-    (every store's sum of squares must precede it).  scalars (optional): [11] = the pre-clip norm, [12] = the applied scale."""
+    (every store's sum of squares must precede it).  scalars (optional): [11] = the pre-clip norm, [12] = the applied scale.
+    lr: a float or a DeviceRate (arcvae_adam_step asks for scalars with a clip part: every store then writes the same norm,
+    scale and rate to ws.scalars[11..13])."""
+    if isinstance(lr, DeviceRate):
+        adam_step(store, lr, guards, ws.scalars, clip=(ws, clip_norm))
+        return
     call("arcvae_adam_update_clipped", ptr(store.flat), ptr(store.grad), ptr(store.adam_m), ptr(store.adam_v),
          C.c_long(store.numel_padded), float(lr), 0.9, 0.999, 1e-8, guards[0], guards[1], ptr(ws.clip_part),
          C.c_long(ws.clip_part.numel()), float(clip_norm), ptr(scalars), stream_ptr())
@@ -1170,6 +1210,22 @@ class StepEngine:
             ws.hyper.copy_(torch.tensor(list(vals) + [0.0, 0.0], dtype=torch.float32))
             ws._hyper_vals = vals
 
+    def set_rate(self, ws: Workspace, lr) -> DeviceRate:
+        """Device-rate mode: lr (finite, >= 0, else ValueError), rounded to fp32, into the workspace's rate word; returns the
+        DeviceRate the step's update launches read.  A fill launch on the CURRENT stream with the value as its own argument
+        (nothing the host could overwrite before it executes), eager and never part of a captured segment: like load_inputs it
+        sits in main's stream order between two steps -- behind the previous step's finish, which joined side and aux (the
+        decoder's update on side included), and ahead of everything of this step (side and aux start behind main's signals).
+        Skipped when the word already holds the value."""
+        v = float(lr)
+        if not (np.isfinite(v) and v >= 0.0):
+            raise ValueError(f"the learning rate must be finite and >= 0, got {lr!r}")
+        v = float(np.float32(v))
+        if ws._rate_val != v:
+            ws.rate.word.fill_(v)
+            ws._rate_val = v
+        return ws.rate
+
     def load_inputs(self, ws: Workspace, x, cond, eps=None, coins=None) -> None:
         dev = self.device
         # device-resident inputs of the workspace's own dtypes: ONE copy launch instead of four (csrc/misc.hip)
@@ -1193,9 +1249,9 @@ class StepEngine:
             ck = torch.as_tensor(np.asarray(coins).astype(np.uint8))
             ws.coins.copy_(ck.to(dev))
 
-    def runner(self, ws: Workspace, lr: float, global_rows: int, capture: bool, clip: Optional[float] = None) -> SegmentRunner:
+    def runner(self, ws: Workspace, lr, global_rows: int, capture: bool, clip: Optional[float] = None) -> SegmentRunner:
         # (clip: segments recorded with the clip's order are never replayed without it, nor the reverse)
-        key = (ws.B, ws.T, float(lr), float(self.hyper_host["free_bits"]), int(global_rows), bool(capture))
+        key = (ws.B, ws.T, lr_key(lr), float(self.hyper_host["free_bits"]), int(global_rows), bool(capture))
         if clip is not None:
             key += (float(clip),)
         if key not in self._runners:
@@ -1318,12 +1374,15 @@ class StepEngine:
             if gates is not None:
                 gates.join()
             ga, gb = self.guards(ws)
+            dev = isinstance(lr, DeviceRate)   # device-rate mode: every update below is an arcvae_adam_step launch
             if clip is not None:
                 if dec_sumsq:
                     grad_sumsq(self.dec, ws, "dec")
                 grad_sumsq(self.enc, ws, "enc")
                 adam_update_clipped(self.dec, lr, ws, clip, (ga, gb))
-                if with_recon:
+                if with_recon and dev:
+                    adam_step(self.enc, lr, (ga, gb), ws.scalars, fin=(ws, self.d.Z), clip=(ws, clip))
+                elif with_recon:
                     st = self.enc
                     call("arcvae_adam_update_finalize_clipped", ptr(st.flat), ptr(st.grad), ptr(st.adam_m), ptr(st.adam_v),
                          C.c_long(st.numel_padded), float(lr), 0.9, 0.999, 1e-8, ga, gb, ptr(ws.rowloss), ws.B, ptr(ws.stats),
@@ -1340,9 +1399,12 @@ class StepEngine:
                 if dec_adam:
                     adam_update(self.dec, lr, guards=(ga, gb))
                 st = self.enc
-                call("arcvae_adam_update_finalize", ptr(st.flat), ptr(st.grad), ptr(st.adam_m), ptr(st.adam_v),
-                     C.c_long(st.numel_padded), float(lr), 0.9, 0.999, 1e-8, ga, gb, ptr(ws.rowloss), ws.B, ptr(ws.stats),
-                     ptr(ws.scalars), self.d.Z, ws.T, stream_ptr())
+                if dev:
+                    adam_step(st, lr, (ga, gb), ws.scalars, fin=(ws, self.d.Z))
+                else:
+                    call("arcvae_adam_update_finalize", ptr(st.flat), ptr(st.grad), ptr(st.adam_m), ptr(st.adam_v),
+                         C.c_long(st.numel_padded), float(lr), 0.9, 0.999, 1e-8, ga, gb, ptr(ws.rowloss), ws.B, ptr(ws.stats),
+                         ptr(ws.scalars), self.d.Z, ws.T, stream_ptr())
                 if self.prop is not None:
                     adam_update(self.prop, lr, guards=(ga, gb))
                 return
@@ -1354,7 +1416,7 @@ class StepEngine:
             if update:
                 if dec_adam:
                     adam_update(self.dec, lr, guards=(ga, gb))
-                adam_update(self.enc, lr, guards=(ga, gb))
+                adam_update(self.enc, lr, guards=(ga, gb), scalars=ws.scalars)
                 if self.prop is not None:
                     adam_update(self.prop, lr, guards=(ga, gb))
         return fin
@@ -1437,10 +1499,13 @@ class StepEngine:
         return self._results(ws)
 
     def train_step(self, x, cond, eps, coins, lr: float, update: bool = True, clip_norm: Optional[float] = None,
-                   **hyper) -> Dict[str, torch.Tensor]:
+                   lr_device: bool = False, **hyper) -> Dict[str, torch.Tensor]:
         """loss + grads (+ Adam) for one minibatch; single process (see dp.py for N ranks).  clip_norm (opt-in, DESIGN.md
         section 10): the updates apply the global-norm clip with that max_norm; the result then also holds "grad_norm" (the
-        pre-clip norm) and "clip_scale" (the applied scale, 1 when not clipping).  store.grad keeps the unclipped gradients."""
+        pre-clip norm) and "clip_scale" (the applied scale, 1 when not clipping).  store.grad keeps the unclipped gradients.
+        lr_device (opt-in, with update): the rate travels as a device word instead of a launch argument,
+        so one captured set of segments serves every rate (learning-rate schedules); the result then holds "lr", the rate the
+        encoder's update applied."""
         clip = check_clip_norm(clip_norm)
         if clip is not None and not update:
             raise ValueError("clip_norm needs an update to clip (update=True, with lr)")
@@ -1448,16 +1513,20 @@ class StepEngine:
         ws = self.workspace(B, T, train=True)
         self.set_hyper(ws, **hyper)
         self.load_inputs(ws, x, cond, eps, coins)
-        self.run_step(ws, lr, update, clip_norm=clip)
-        return self._results(ws, clip=clip is not None)
+        self.run_step(ws, lr, update, clip_norm=clip, lr_device=lr_device)
+        return self._results(ws, clip=clip is not None, rate=lr_device and update)
 
-    def run_step(self, ws: Workspace, lr: float, update: bool = True, clip_norm: Optional[float] = None) -> None:
-        """Enqueue (or replay) the step on the current stream; inputs/hyper already in `ws`."""
+    def run_step(self, ws: Workspace, lr, update: bool = True, clip_norm: Optional[float] = None,
+                 lr_device: bool = False) -> None:
+        """Enqueue (or replay) the step on the current stream; inputs/hyper already in `ws`.  lr_device: lr goes to the
+        workspace's rate word first (set_rate: eager, ahead of any replay)."""
         clip = check_clip_norm(clip_norm) if update else None
+        if lr_device and update:
+            lr = self.set_rate(ws, lr)
         if clip is not None:
             self.clip_workspace(ws)
         if self.mode == "graph":
-            key = (ws.B, ws.T, float(lr), float(self.hyper_host["free_bits"]), bool(update))
+            key = (ws.B, ws.T, lr_key(lr), float(self.hyper_host["free_bits"]), bool(update))
             if clip is not None:             # a graph captured without the clip is never replayed with it
                 key += (clip,)
             g = self._graphs.get(key)
@@ -1475,12 +1544,14 @@ class StepEngine:
             run = self.runner(ws, -1.0, ws.B, capture=(self.mode == "segments"))
         self._enqueue_step(ws, lr, ws.B, update, run, clip=clip)
 
-    def _results(self, ws: Workspace, clip: bool = False) -> Dict[str, torch.Tensor]:
+    def _results(self, ws: Workspace, clip: bool = False, rate: bool = False) -> Dict[str, torch.Tensor]:
         out = {k: ws.scalars[i] for i, k in enumerate(SCALAR_KEYS)}
         out["mu"], out["logvar"], out["z"] = ws.mu, ws.logvar, ws.z
         out["step_status"] = ws.scalars[15]   # 1.0: a gate expired / a persistent sweep gave up (values NaN, no update)
         if clip:
             out["grad_norm"], out["clip_scale"] = ws.scalars[11], ws.scalars[12]   # NaN, NaN when the update was skipped
+        if rate:
+            out["lr"] = ws.scalars[13]        # the rate word as the encoder's update read it
         return out
 
     def gather_logits(self, ws: Workspace) -> torch.Tensor:

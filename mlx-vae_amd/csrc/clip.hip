@@ -13,7 +13,7 @@
 //                      is the reduction's barrier: no float atomics, no last-block hand-off.  Block 0 writes the pre-clip norm
 //                      to scalars[11] and the applied scale to scalars[12] (NaN, NaN on a tripped guard: nothing is applied).
 // The gradient buffers themselves are never written: they keep the unclipped gradients.
-#include "common.h"
+#include "ops.h"
 #include <algorithm>
 #include <cmath>
 
@@ -66,13 +66,17 @@ struct ClipFinalize {            // as misc.hip's AdamFinalize: the single-proce
     const float* rowloss; float* stats; int B, Z, T;
 };
 
+// DEV: the device-rate form (arcvae_adam_step; misc.hip's adam_kernel has the contract): lr = *lr_dev, scalars[13] = lr.
+template <bool DEV>
 __global__ __launch_bounds__(CLIP_THREADS) void adam_clip_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                                  float* __restrict__ m, float* __restrict__ v, long n4, long n,
-                                                                 float lr, float b1, float b2, float omb1, float omb2, float eps,
+                                                                 float lr_val, const float* lr_dev, float b1, float b2,
+                                                                 float omb1, float omb2, float eps,
                                                                  const unsigned* guard_a, const unsigned* guard_b,
                                                                  const float* __restrict__ partials, int np, double max_norm,
                                                                  float* scalars, ClipFinalize fin) {
 #pragma clang fp contract(off)
+    const float lr = DEV ? *lr_dev : lr_val;
     const bool tripped = (guard_a && __hip_atomic_load(guard_a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) ||
                          (guard_b && __hip_atomic_load(guard_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
     // the launch-boundary reduce: every block, all partials, one order
@@ -110,9 +114,11 @@ __global__ __launch_bounds__(CLIP_THREADS) void adam_clip_kernel(float* __restri
         if (scalars && threadIdx.x == 0) {
             scalars[11] = tripped ? __builtin_nanf("") : norm;
             scalars[12] = tripped ? __builtin_nanf("") : scale;
+            if (DEV) scalars[13] = lr;
         }
     }
     if (tripped) return;
+    if (DEV && !(lr >= 0.f && lr <= 3.402823466e+38f)) return;      // negative, infinite, NaN: nothing is updated
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         float4 pp = reinterpret_cast<float4*>(p)[i];
@@ -143,7 +149,8 @@ __global__ __launch_bounds__(CLIP_THREADS) void adam_clip_kernel(float* __restri
     }
 }
 
-int launch_adam_clip(float* params, const float* grads, float* m, float* v, long n, double lr, double beta1, double beta2,
+int launch_adam_clip(float* params, const float* grads, float* m, float* v, long n, double lr, const float* lr_dev,
+                     double beta1, double beta2,
                      double eps, const unsigned* guard_a, const unsigned* guard_b, const float* partials, long n_partials,
                      double max_norm, float* scalars, ClipFinalize fin, hipStream_t stream) {
     const uintptr_t al = reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
@@ -152,9 +159,14 @@ int launch_adam_clip(float* params, const float* grads, float* m, float* v, long
     const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);   // as arcvae_adam_update
     const long work = n4 > 0 ? n4 : n;
     const int blocks = (int)std::min((long)2048, (work + 255) / 256);
-    hipLaunchKernelGGL(adam_clip_kernel, dim3(blocks), dim3(CLIP_THREADS), 0, stream, params, grads, m, v, n4, n, (float)lr,
-                       (float)beta1, (float)beta2, omb1, omb2, (float)eps, guard_a, guard_b, partials, (int)n_partials,
-                       max_norm, scalars, fin);
+    if (lr_dev)
+        hipLaunchKernelGGL(adam_clip_kernel<true>, dim3(blocks), dim3(CLIP_THREADS), 0, stream, params, grads, m, v, n4, n, 0.f,
+                           lr_dev, (float)beta1, (float)beta2, omb1, omb2, (float)eps, guard_a, guard_b, partials,
+                           (int)n_partials, max_norm, scalars, fin);
+    else
+        hipLaunchKernelGGL(adam_clip_kernel<false>, dim3(blocks), dim3(CLIP_THREADS), 0, stream, params, grads, m, v, n4, n,
+                           (float)lr, (const float*)nullptr, (float)beta1, (float)beta2, omb1, omb2, (float)eps, guard_a, guard_b,
+                           partials, (int)n_partials, max_norm, scalars, fin);
     return arcvae_launch_status();
 }
 
@@ -186,7 +198,7 @@ extern "C" int arcvae_adam_update_clipped(float* params, const float* grads, flo
     if (!params || !grads || !m || !v || n <= 0 || !clip_args_ok(partials, n_partials, max_norm)) return ARCVAE_ERR_ARG;
     ClipFinalize fin;
     fin.rowloss = nullptr; fin.stats = nullptr; fin.B = fin.Z = fin.T = 0;
-    return launch_adam_clip(params, grads, m, v, n, lr, beta1, beta2, eps, guard_a, guard_b, partials, n_partials, max_norm,
+    return launch_adam_clip(params, grads, m, v, n, lr, nullptr, beta1, beta2, eps, guard_a, guard_b, partials, n_partials, max_norm,
                             scalars, fin, stream);
 }
 
@@ -200,6 +212,25 @@ extern "C" int arcvae_adam_update_finalize_clipped(float* params, const float* g
         return ARCVAE_ERR_ARG;
     ClipFinalize fin;
     fin.rowloss = rowloss; fin.stats = stats; fin.B = B; fin.Z = Z; fin.T = T;
-    return launch_adam_clip(params, grads, m, v, n, lr, beta1, beta2, eps, guard_a, guard_b, partials, n_partials, max_norm,
+    return launch_adam_clip(params, grads, m, v, n, lr, nullptr, beta1, beta2, eps, guard_a, guard_b, partials, n_partials, max_norm,
                             scalars, fin, stream);
+}
+
+// Every update form with the learning rate read from DEVICE memory (learning-rate schedules): one captured
+// launch serves every rate.  rowloss non-null: the finalize part (arcvae_adam_update_finalize); partials non-null: the clip part
+// (arcvae_adam_update_clipped); both: arcvae_adam_update_finalize_clipped.  With *lr_dev == (float)lr bitwise the by-value forms.
+extern "C" int arcvae_adam_step(float* params, const float* grads, float* m, float* v, long n, const float* lr_dev,
+                                double beta1, double beta2, double eps, const unsigned* guard_a, const unsigned* guard_b,
+                                const float* rowloss, int B, float* stats, float* scalars, int Z, int T,
+                                const float* partials, long n_partials, double max_norm, hipStream_t stream) {
+    if (!params || !grads || !m || !v || !lr_dev || n <= 0) return ARCVAE_ERR_ARG;
+    if (rowloss && (!stats || !scalars || B <= 0 || Z <= 0 || T <= 0)) return ARCVAE_ERR_ARG;
+    if (partials && (!scalars || !clip_args_ok(partials, n_partials, max_norm))) return ARCVAE_ERR_ARG;
+    if (!partials)
+        return arcvae_adam_step_plain(params, grads, m, v, n, lr_dev, beta1, beta2, eps, guard_a, guard_b, rowloss, B, stats,
+                                      scalars, Z, T, stream);
+    ClipFinalize fin;
+    fin.rowloss = rowloss; fin.stats = stats; fin.B = B; fin.Z = Z; fin.T = T;
+    return launch_adam_clip(params, grads, m, v, n, 0.0, lr_dev, beta1, beta2, eps, guard_a, guard_b, partials, n_partials,
+                            max_norm, scalars, fin, stream);
 }

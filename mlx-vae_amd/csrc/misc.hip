@@ -326,16 +326,24 @@ __global__ void transpose_tokens_kernel(const int32_t* __restrict__ src, int32_t
 // fin (optional, arcvae_adam_update_finalize): the single-process step's loss finalize -- CE row sums -> stats[2Z+3], recon and
 // total scalars, the guard's NaN poison (latent.hip: recon_finalize_kernel) -- done by block 0 of THIS launch: one kernel less in
 // the exposed tail of the step (round 4).
+// DEV (arcvae_adam_step: learning-rate schedules): the rate is the fp32 word *lr_dev, read at execution
+// time, so a captured launch serves every rate; the arithmetic is the by-value form's, expression for expression.  Block 0
+// reports the word in rate_out[13] (optional).  A word that is negative, infinite or NaN updates nothing -- the finalize part
+// still writes its scalars, the same split as a tripped guard, but does not poison them: the gradients are sound.
 struct AdamFinalize {
     const float* rowloss; float* stats; float* scalars; int B, Z, T;
 };
+template <bool DEV>
 __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const float* __restrict__ g,
                                                    float* __restrict__ m, float* __restrict__ v, long n4, long n,
-                                                   float lr, float b1, float b2, float omb1, float omb2, float eps,
+                                                   float lr_val, const float* lr_dev, float* rate_out, float b1, float b2,
+                                                   float omb1, float omb2, float eps,
                                                    const unsigned* guard_a, const unsigned* guard_b, AdamFinalize fin) {
 #pragma clang fp contract(off)
+    const float lr = DEV ? *lr_dev : lr_val;
     const bool tripped = (guard_a && __hip_atomic_load(guard_a, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u) ||
                          (guard_b && __hip_atomic_load(guard_b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT) != 0u);
+    if (DEV && rate_out && blockIdx.x == 0 && threadIdx.x == 0) rate_out[13] = lr;
     if (fin.rowloss && blockIdx.x == 0) {
         float s = 0.f;
         for (int i = threadIdx.x; i < fin.B; i += 256) s += fin.rowloss[i];
@@ -358,6 +366,7 @@ __global__ __launch_bounds__(256) void adam_kernel(float* __restrict__ p, const 
         }
     }
     if (tripped) return;
+    if (DEV && !(lr >= 0.f && lr <= 3.402823466e+38f)) return;      // negative, infinite, NaN: nothing is updated
     const long stride = (long)gridDim.x * blockDim.x;
     for (long i = (long)blockIdx.x * blockDim.x + threadIdx.x; i < n4; i += stride) {
         float4 pp = reinterpret_cast<float4*>(p)[i];
@@ -569,12 +578,12 @@ extern "C" int arcvae_transpose_tokens(const int32_t* src, int32_t* dst, int B, 
     return arcvae_launch_status();
 }
 
-// Reference: trainer.py:320,324 (optimizer.update) with MLX optim.Adam defaults (Q7).
-// guard_a / guard_b: optional device words; the update is skipped when either is non-zero (see adam_kernel).
-extern "C" int arcvae_adam_update(float* params, const float* grads, float* m, float* v, long n,
-                                  double lr, double beta1, double beta2, double eps, const unsigned* guard_a,
-                                  const unsigned* guard_b, hipStream_t stream) {
-    if (!params || !grads || !m || !v || n <= 0) return ARCVAE_ERR_ARG;
+// The one launcher of adam_kernel: lr_dev null = the by-value forms (rate `lr`), else the device-rate form of arcvae_adam_step
+// (clip.hip), which reports the word in rate_out[13] when rate_out is given.  Arguments are checked by the callers.
+namespace {
+int launch_adam(float* params, const float* grads, float* m, float* v, long n, double lr, const float* lr_dev,
+                       float* rate_out, double beta1, double beta2, double eps, const unsigned* guard_a,
+                       const unsigned* guard_b, AdamFinalize fin, hipStream_t stream) {
     const uintptr_t al = reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
                          reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v);
     const long n4 = (al & 15) ? 0 : n / 4;
@@ -582,11 +591,34 @@ extern "C" int arcvae_adam_update(float* params, const float* grads, float* m, f
     const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
     const long work = n4 > 0 ? n4 : n;
     const int blocks = (int)min((long)2048, (work + 255) / 256);
+    if (lr_dev)
+        hipLaunchKernelGGL(adam_kernel<true>, dim3(blocks), dim3(256), 0, stream, params, grads, m, v, n4, n, 0.f, lr_dev,
+                           rate_out, (float)beta1, (float)beta2, omb1, omb2, (float)eps, guard_a, guard_b, fin);
+    else
+        hipLaunchKernelGGL(adam_kernel<false>, dim3(blocks), dim3(256), 0, stream, params, grads, m, v, n4, n, (float)lr,
+                           (const float*)nullptr, (float*)nullptr, (float)beta1, (float)beta2, omb1, omb2, (float)eps, guard_a,
+                           guard_b, fin);
+    return arcvae_launch_status();
+}
+}  // namespace
+
+int arcvae_adam_step_plain(float* params, const float* grads, float* m, float* v, long n, const float* lr_dev, double beta1,
+                           double beta2, double eps, const unsigned* guard_a, const unsigned* guard_b, const float* rowloss,
+                           int B, float* stats, float* scalars, int Z, int T, hipStream_t stream) {
+    AdamFinalize fin;
+    fin.rowloss = rowloss; fin.stats = stats; fin.scalars = scalars; fin.B = B; fin.Z = Z; fin.T = T;
+    return launch_adam(params, grads, m, v, n, 0.0, lr_dev, scalars, beta1, beta2, eps, guard_a, guard_b, fin, stream);
+}
+
+// Reference: trainer.py:320,324 (optimizer.update) with MLX optim.Adam defaults (Q7).
+// guard_a / guard_b: optional device words; the update is skipped when either is non-zero (see adam_kernel).
+extern "C" int arcvae_adam_update(float* params, const float* grads, float* m, float* v, long n,
+                                  double lr, double beta1, double beta2, double eps, const unsigned* guard_a,
+                                  const unsigned* guard_b, hipStream_t stream) {
+    if (!params || !grads || !m || !v || n <= 0) return ARCVAE_ERR_ARG;
     AdamFinalize fin;
     fin.rowloss = nullptr; fin.stats = nullptr; fin.scalars = nullptr; fin.B = fin.Z = fin.T = 0;
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, stream, params, grads, m, v, n4, n, (float)lr,
-                       (float)beta1, (float)beta2, omb1, omb2, (float)eps, guard_a, guard_b, fin);
-    return arcvae_launch_status();
+    return launch_adam(params, grads, m, v, n, lr, nullptr, nullptr, beta1, beta2, eps, guard_a, guard_b, fin, stream);
 }
 
 // arcvae_recon_finalize + arcvae_adam_update in ONE launch (the tail of the single-process step: trainer.py:320-366 reads the
@@ -597,17 +629,9 @@ extern "C" int arcvae_adam_update_finalize(float* params, const float* grads, fl
                                            const unsigned* guard_b, const float* rowloss, int B, float* stats, float* scalars,
                                            int Z, int T, hipStream_t stream) {
     if (!params || !grads || !m || !v || n <= 0 || !rowloss || !stats || !scalars || B <= 0 || Z <= 0 || T <= 0) return ARCVAE_ERR_ARG;
-    const uintptr_t al = reinterpret_cast<uintptr_t>(params) | reinterpret_cast<uintptr_t>(grads) |
-                         reinterpret_cast<uintptr_t>(m) | reinterpret_cast<uintptr_t>(v);
-    const long n4 = (al & 15) ? 0 : n / 4;
-    const float omb1 = (float)(1.0 - beta1), omb2 = (float)(1.0 - beta2);
-    const long work = n4 > 0 ? n4 : n;
-    const int blocks = (int)min((long)2048, (work + 255) / 256);
     AdamFinalize fin;
     fin.rowloss = rowloss; fin.stats = stats; fin.scalars = scalars; fin.B = B; fin.Z = Z; fin.T = T;
-    hipLaunchKernelGGL(adam_kernel, dim3(blocks), dim3(256), 0, stream, params, grads, m, v, n4, n, (float)lr,
-                       (float)beta1, (float)beta2, omb1, omb2, (float)eps, guard_a, guard_b, fin);
-    return arcvae_launch_status();
+    return launch_adam(params, grads, m, v, n, lr, nullptr, nullptr, beta1, beta2, eps, guard_a, guard_b, fin, stream);
 }
 
 // x[r*ld + c] = 0 for r < rows, c < cols.  A kernel rather than hipMemsetAsync: memset NODES of a captured

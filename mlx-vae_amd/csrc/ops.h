@@ -27,3 +27,7 @@ int arcvae_gemm_skinny_pair(int transB, const int* M, const int* N, const int* K
                             const float* const* B, const int* ldb, float* const* C, const int* ldc,
                             const float* const* bias, const int* flags, hipStream_t stream);
 
+// internal (C++ linkage): the unclipped forms of arcvae_adam_step (clip.hip) on misc.hip's adam_kernel; arguments checked there
+int arcvae_adam_step_plain(float* params, const float* grads, float* m, float* v, long n, const float* lr_dev, double beta1,
+                           double beta2, double eps, const unsigned* guard_a, const unsigned* guard_b, const float* rowloss,
+                           int B, float* stats, float* scalars, int Z, int T, hipStream_t stream);

@@ -5,7 +5,8 @@ Drop-in for the reference's `python train.py ...` (train.py:17-255): identical f
 argparse defaults (note Q17: these are the ARGPARSE defaults, not the README's), identical seed,
 80/10/10 split, checkpoint clearing / `--resume` behaviour, history keys and output files.
 Additive flags: --device, --synthetic N (generate a SELFIES-shaped dataset when the JSON is absent;
-the reference's dataset blob is not distributed), --no_progress, --precision, --world_size / --dist_backend.
+the reference's dataset blob is not distributed), --no_progress, --precision, --world_size / --dist_backend, --grad_clip_mode, --property_predictor_hidden, --lr_schedule /
+--warmup_steps / --min_lr_ratio.
 
 Data parallel over the GPUs of one node (the reference is single-process):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29544 \
@@ -74,6 +75,13 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--property_predictor_hidden", type=int, default=0,
                     help="hidden width of a property predictor on z trained with --lambda_prop (extension; 0 = no predictor, "
                          "--lambda_prop is then unused as in the reference)")
+    ap.add_argument("--lr_schedule", choices=["constant", "linear", "cosine"], default=None,
+                    help="per-step learning-rate schedule on --learning_rate (extension; default: none, one rate): linear warmup "
+                         "over --warmup_steps, then constant, or linear / cosine decay to --min_lr_ratio * --learning_rate over "
+                         "epochs * (train rows // batch_size) steps")
+    ap.add_argument("--warmup_steps", type=int, default=None, help="warmup steps of --lr_schedule (default 0)")
+    ap.add_argument("--min_lr_ratio", type=float, default=None, help="final rate of --lr_schedule as a fraction of "
+                                                                     "--learning_rate (default 0)")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default=None,
                     help="fp32: the parity path (default); bf16: throughput mode -- matrix products on bf16 operands with "
                          "f32 accumulation, parameters and optimizer state in f32 (extension; ARCVAE_PRECISION does the same)")
@@ -114,8 +122,16 @@ def init_data_parallel(args):
     return rank, world
 
 
+def parse_args(argv=None):
+    ap = build_parser()
+    args = ap.parse_args(argv)
+    if args.lr_schedule is None and (args.warmup_steps is not None or args.min_lr_ratio is not None):
+        ap.error("--warmup_steps / --min_lr_ratio need --lr_schedule")
+    return args
+
+
 def main(argv=None):
-    args = build_parser().parse_args(argv)
+    args = parse_args(argv)
     if args.precision:                      # read when the step engine of the model is created (arcvae_hip/engine.py)
         os.environ["ARCVAE_PRECISION"] = args.precision
     if args.property_predictor_hidden and (args.world_size or int(os.environ.get("WORLD_SIZE", "1"))) > 1:
@@ -196,13 +212,19 @@ def main(argv=None):
         from models.property_predictor import PropertyPredictor
         predictor = PropertyPredictor(args.latent_dim, args.num_conditions, args.property_predictor_hidden, device=args.device)
         print(f"  Property predictor: hidden={args.property_predictor_hidden}, lambda_prop={args.lambda_prop}")
+    schedule = None
+    if args.lr_schedule is not None:
+        from lr_schedule import LRSchedule
+        schedule = LRSchedule(args.learning_rate, args.lr_schedule, warmup_steps=args.warmup_steps or 0,
+                              min_lr_ratio=args.min_lr_ratio or 0.0)     # total_steps: the trainer fills it in
+        print(f"  LR schedule: {args.lr_schedule}, warmup_steps={schedule.warmup_steps}, min_lr_ratio={schedule.min_lr_ratio}")
     trainer = ARCVAETrainerWithLoss(
         encoder=vae.encoder, decoder=vae.decoder, property_predictor=predictor, dataset=train_dataset,
         batch_size=args.batch_size, learning_rate=args.learning_rate, beta_start=args.beta_start,
         beta_end=args.beta_end, beta_warmup_epochs=args.beta_warmup_epochs, lambda_prop=args.lambda_prop,
         lambda_collapse=args.lambda_collapse, free_bits=args.free_bits, lambda_mi=args.lambda_mi,
         grad_clip=args.grad_clip, checkpoint_dir=args.checkpoint_dir, progress=not args.no_progress,
-        grad_clip_mode=args.grad_clip_mode)
+        grad_clip_mode=args.grad_clip_mode, lr_schedule=schedule)
     if args.resume:
         loaded = trainer.load_checkpoint(str(checkpoint_dir / "checkpoint_best.npz"))
         start_epoch = loaded + 1  # best_val_loss restarts at inf, as in the reference (Q21)
@@ -215,7 +237,8 @@ def main(argv=None):
         for k in ("train_loss", "train_recon", "train_kl", "train_collapse", "train_prop", "val_loss", "val_recon",
                   "val_kl", "val_collapse", "val_prop", "beta", "teacher_forcing", "mutual_info"):
             trainer.history[k].append(metrics[k])
-        trainer.history["learning_rate"].append(args.learning_rate)
+        if schedule is None:                     # (with --lr_schedule the trainer appends the epoch's last rate itself)
+            trainer.history["learning_rate"].append(args.learning_rate)
         if "grad_norm" in trainer.history:       # --grad_clip_mode global_norm: epoch mean of the pre-clip norms
             trainer.history["grad_norm"].append(metrics["grad_norm"])
         is_best = metrics["val_loss"] < best_val_loss

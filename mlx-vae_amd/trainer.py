@@ -23,6 +23,12 @@ Property predictor (an extension; the reference's own bran
 lambda_prop weighs its loss, train_prop / val_prop are real, and the checkpoints carry `predictor_weights/<name>` and
 `predictor_optimizer_state/{m,v}/<name>`.  Not combined with data parallelism (refused).
 
+Learning-rate schedules (an extension): with `lr_schedule=` an lr_schedule.LRSchedule the rate of
+every step is schedule.lr(global_step) -- global_step counts every step the trainer launched -- handed to the step as a device
+word (lr_device=True: the same captured step replays at every rate).  history["learning_rate"] then holds the rate of each
+epoch's last step, and the checkpoints carry `global_step` and `lr_schedule_json`, so a resumed run continues the curve.
+`lr_schedule=None` (default) is the one-rate trainer, launch for launch, with the checkpoint keys as they are.
+
 Data parallelism (the reference is single-process): under `torch.distributed` (train.py started by
 `python -m torch.distributed.run`, one process per GPU) every rank runs THIS epoch flow on the same dataset order and the
 same coins (one seeded NumPy stream), every batch is the GLOBAL batch, and the step / the loss forwards work on the
@@ -54,7 +60,8 @@ class ARCVAETrainerWithLoss:
                  batch_size: int = 32, beta_start: float = 0.0, beta_end: float = 0.4,
                  beta_warmup_epochs: int = 100, lambda_prop: float = 0.1, lambda_collapse: float = 0.01,
                  free_bits: float = 0.5, lambda_mi: float = 0.01, grad_clip: float = 1.0,
-                 checkpoint_dir: str = "./checkpoints", progress: bool = True, grad_clip_mode: str = "reference"):
+                 checkpoint_dir: str = "./checkpoints", progress: bool = True, grad_clip_mode: str = "reference",
+                 lr_schedule=None):
         self.encoder, self.decoder, self.property_predictor = encoder, decoder, property_predictor
         self.dataset, self.batch_size, self.grad_clip = dataset, batch_size, grad_clip
         if grad_clip_mode not in ("reference", "global_norm"):
@@ -66,6 +73,13 @@ class ARCVAETrainerWithLoss:
         self.free_bits, self.lambda_mi = free_bits, lambda_mi
         self.beta_start, self.beta_end, self.beta_warmup_epochs = beta_start, beta_end, beta_warmup_epochs
         self.learning_rate = learning_rate
+        if lr_schedule is not None:
+            from lr_schedule import LRSchedule
+            if not isinstance(lr_schedule, LRSchedule):
+                raise ValueError(f"lr_schedule must be an lr_schedule.LRSchedule or None, got {type(lr_schedule).__name__}")
+        self.lr_schedule = lr_schedule
+        self.global_step = 0         # steps launched so far (schedule mode; batches the explosion check skips included)
+        self.last_lr = None          # the rate of the last step launched (schedule mode)
         self.checkpoint_dir = Path(checkpoint_dir)
         self.checkpoint_dir.mkdir(exist_ok=True)
         self.progress = progress
@@ -98,9 +112,15 @@ class ARCVAETrainerWithLoss:
         """loss + grads + (no-op clip, Q6, or the global-norm clip) + both Adam updates: one captured step (N ranks:
         arcvae_hip.dp).  Returns [total_loss, step status] of the GLOBAL batch as one tensor -- [total_loss, step status,
         pre-clip norm] with the global-norm clip: read together, one host sync per batch."""
+        rate = {}
+        if self.lr_schedule is not None:     # the schedule's rate of this step, as a device word
+            self.last_lr = self.lr_schedule.lr(self.global_step)
+            self.global_step += 1
+            rate = dict(lr_device=True)
         out, _ = api.value_and_grad(self.encoder, self.decoder, molecules, conditions,
-                                    teacher_forcing_ratio=teacher_forcing_ratio, lr=self.learning_rate,
-                                    predictor=self.property_predictor, grad_clip=self.clip_norm, **hyper)
+                                    teacher_forcing_ratio=teacher_forcing_ratio,
+                                    lr=self.last_lr if self.lr_schedule is not None else self.learning_rate,
+                                    predictor=self.property_predictor, grad_clip=self.clip_norm, **rate, **hyper)
         return out["loss_status_norm"] if self.clip_norm is not None else out["loss_and_status"]
 
     def _encode(self, molecules, conditions):
@@ -158,7 +178,11 @@ class ARCVAETrainerWithLoss:
     def train_epoch(self, epoch: int, total_epochs: int, val_dataset=None) -> Dict[str, float]:
         beta = self.compute_beta(epoch)
         tf = self.compute_teacher_forcing_ratio(epoch, total_epochs)
+        if self.lr_schedule is not None and self.lr_schedule.total_steps is None:
+            self.lr_schedule.set_total_steps(total_epochs * (len(self.dataset) // self.batch_size))
         self.last_train_metrics = self._train_epoch_batches(beta, tf)
+        if self.lr_schedule is not None:
+            self.history["learning_rate"].append(self.last_lr)       # the rate of the epoch's last step
         extra = {"grad_norm": self.last_train_metrics["grad_norm"]} if "grad_norm" in self.last_train_metrics else {}
         if self.engine is not None:
             self.engine.check_gates()  # a device-side gate that expired would mean the step's streams lost their order
@@ -274,6 +298,9 @@ class ARCVAETrainerWithLoss:
                 ck[f"{tag}_optimizer_state/m/{n}"] = st._view(st.adam_m, n).cpu().numpy()
                 ck[f"{tag}_optimizer_state/v/{n}"] = st._view(st.adam_v, n).cpu().numpy()
         ck["learning_rate"] = np.array(self.learning_rate)
+        if self.lr_schedule is not None:
+            ck["global_step"] = np.array(self.global_step)
+            ck["lr_schedule_json"] = np.array(json.dumps(self.lr_schedule.state()))
         if self.persist_best_val:
             ck["best_val_loss"] = np.array(self.best_val_loss)
         if is_best:
@@ -297,6 +324,10 @@ class ARCVAETrainerWithLoss:
                     st._view(st.adam_v, n).copy_(torch.from_numpy(ck[f"{tag}_optimizer_state/v/{n}"]))
         if "history_json" in ck:
             self.history = json.loads(str(ck["history_json"]))
+        if self.lr_schedule is not None and "global_step" in ck:     # continue the curve where the run stopped
+            from lr_schedule import LRSchedule
+            self.global_step = int(ck["global_step"])
+            self.lr_schedule = LRSchedule.from_state(json.loads(str(ck["lr_schedule_json"])))
         return int(ck["epoch"]) if "epoch" in ck else 0
 
     def save_history(self, path: str):
