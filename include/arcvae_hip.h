@@ -49,7 +49,12 @@ extern "C" {
 #define ARCVAE_GEMM_SPLIT3 512    /* any layout: every f32 operand as three bf16 pieces (8+8+8 bits), the six products of weight
                                    * >= 2^-16 on v_mfma_f32_32x32x16_bf16, f32 accumulate -- the accuracy class of the exact-f32
                                    * kernels (a PARITY path) at 2.7x less matrix-pipe time; for GEMMs beside a persistent sweep */
-#define ARCVAE_LSTM_RETILE 1      /* arcvae_enc_lstm_backward flags bit 0: write the BPTT weight layouts first */
+#define ARCVAE_GEMM_QUIET 1024    /* TN "+=" with ARCVAE_GEMM_SPLITK: the split-bf16 arithmetic (three pieces, six products, f32
+                                   * accumulate: a PARITY path) with 128 x 128 block tiles whose operands are staged once in LDS by
+                                   * 16-byte LDS-DMA and shared by the block's waves -- a quarter of the bytes and far fewer load
+                                   * instructions than the LDS-free split kernel: for GEMMs beside the bs-64 BPTT sweep.  Needs
+                                   * M, N, lda, ldb multiples of 4 and 16-byte aligned A, B (ARCVAE_ERR_ARG otherwise) */
+#define ARCVAE_LSTM_RETILE 1     /* arcvae_enc_lstm_backward flags bit 0: write the BPTT weight layouts first */
 #define ARCVAE_LSTM_BF16 2        /* arcvae_enc_lstm_forward / _backward flags bit 1: throughput mode -- bf16 operand copies and
                                    * v_mfma_f32_16x16x32_bf16 products where the shape runs on the register-tiled step kernels
                                    * (the MFMA-bound regime, e.g. H512 L4 bs 512); gates, cell state and accumulators stay f32.
@@ -241,7 +246,9 @@ int arcvae_enc_lstm_backward_fused(const float* const* Wx, const float* const* W
  * bit 2 = dWx_l (l >= 1) and bias sums only, bit 3 = dWh_l only; bit 4 = exact-f32 tile GEMMs instead of the split-bf16
  * kernel; bit 5 = onehot_ws was written by arcvae_enc_prologue; bit 6 = the split-bf16 kernel's 128-row tile (the range
  * runs behind the sweep, no sweep block is resident); bit 8 = dtable_ws was zeroed ahead of the call (arcvae_enc_prologue:
- * the zero-fill launch in front of a `first` range is skipped); bit 10 = the per-layer GEMMs as three-piece tile GEMMs
+ * the zero-fill launch in front of a `first` range is skipped); bit 9 = the per-layer GEMMs of the split-bf16 path on its
+ * LDS-staged "quiet" form (ARCVAE_GEMM_QUIET: fewer bytes and load instructions beside the bs-64 BPTT sweep; ignored with
+ * bits 4, 6, 7, 10, 11); bit 10 = the per-layer GEMMs as three-piece tile GEMMs
  * (ARCVAE_GEMM_SPLIT3: fp32-class accuracy, for the MFMA-bound regime beside the tiled sweeps); bit 7 = throughput mode (one bf16 product per GEMM step instead of
  * the six of the split form: not a parity path); bit 11 = h_oct / dG_oct are the sweeps' three-plane operand rings hseq_t /
  * dG_t with ALL T time slots (arcvae_enc_lstm_operand_slots == T): the per-layer GEMMs read the planes directly (transposing

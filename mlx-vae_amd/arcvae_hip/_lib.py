@@ -20,6 +20,7 @@ GEMM_SPLITK = 4
 GEMM_NO_SKINNY = 8
 GEMM_BF16 = 256      # throughput mode: bf16 operands, f32 accumulate (include/arcvae_hip.h ARCVAE_GEMM_BF16)
 GEMM_SPLIT3 = 512    # three bf16 pieces per operand, six products: fp32-class accuracy (ARCVAE_GEMM_SPLIT3)
+GEMM_QUIET = 1024    # TN "+=" split-bf16 products from LDS-staged 128 x 128 tiles (ARCVAE_GEMM_QUIET)
 LSTM_RETILE = 1      # arcvae_enc_lstm_backward flags
 LSTM_BF16 = 2        # arcvae_enc_lstm_forward / _backward flags: throughput mode (tiled regime)
 LSTM_SPLIT3 = 4      # same places: three bf16 pieces per operand, six products -- a parity path (tiled regime)
@@ -31,6 +32,7 @@ DEC_PART_HEAD = 2048  # arcvae_dec_forward_dense mode / _backward_dense flags bi
 DEC_PART_TAIL = 4096  # ... fc_out only (layers 1 .. L-1 by arcvae_dense_stack_forward / _backward)
 DEC_NO_GPRE = 1024   # arcvae_dec_forward_dense mode bit: forward only, pre-activations not kept (fused GEMM + cell)
 WGRAD_BF16 = 128     # arcvae_enc_lstm_wgrad parts bit
+WGRAD_QUIET = 512    # arcvae_enc_lstm_wgrad parts bit 9: the per-layer GEMMs on the quiet split-bf16 kernel
 
 _vp = C.c_void_p
 _i = C.c_int

@@ -546,6 +546,15 @@ class SegmentRunner:
                 g.replay()
 
 
+WGRAD_QUIET_DEFAULT = "1"
+
+
+def wgrad_quiet() -> bool:
+    """The weight-gradient GEMMs beside the one-row-group persistent BPTT sweep run on the quiet split-bf16 kernel
+    (arcvae_enc_lstm_wgrad parts bit 9); ARCVAE_WGRAD_QUIET=0/1 overrides."""
+    return os.environ.get("ARCVAE_WGRAD_QUIET", WGRAD_QUIET_DEFAULT) != "0"
+
+
 class EncoderBackwardPlan:
     """The pieces of the encoder backward as closures over (enc, ws), plus the chunk schedule.
 
@@ -562,6 +571,9 @@ class EncoderBackwardPlan:
     # dWx GEMMs on side 1.060 / 1.040-1.044 / 1.037 / 1.045 / 1.051).
     FRACTIONS_LAUNCHES = "0.3,0.6,0.85,1.0"
     FRACTIONS_PERSISTENT = "0.63,1.0"
+    # ... with the quiet weight-gradient kernel (one launch per chunk on aux): 0.63 0.910-0.916, 0.67 0.906-0.908,
+    # 0.7 0.904-0.912, 0.73 0.911-0.914, 0.77 / 0.8 0.920 / 0.928, "0.5,0.85,1" 0.932 (profiles/wgrad_quiet_step_ab.txt)
+    FRACTIONS_QUIET = "0.7,1.0"
     FRACTIONS_FUSED = "1.0"      # weight gradients formed inside the sweep: one launch, nothing to hand over
 
     def __init__(self, enc: ParamStore, ws: Workspace, d: ModelDims):
@@ -569,7 +581,11 @@ class EncoderBackwardPlan:
         L, T = d.L, ws.T
         self.persistent = bptt_reduce_scatter_ok(ws, d)
         self.fused = fused_wgrad_ok(ws, d)
-        default = self.FRACTIONS_FUSED if self.fused else (self.FRACTIONS_PERSISTENT if self.persistent else self.FRACTIONS_LAUNCHES)
+        # the weight-gradient GEMMs beside the one-row-group persistent sweep on the quiet split-bf16 kernel (wgrad below)
+        self.quiet = (self.persistent and not self.fused and ws.B <= 64 and wgrad_quiet()
+                      and not getattr(ws, "bf16", False))   # (throughput mode keeps the kernel it was measured with)
+        default = self.FRACTIONS_FUSED if self.fused else (self.FRACTIONS_QUIET if self.quiet else
+                                                           (self.FRACTIONS_PERSISTENT if self.persistent else self.FRACTIONS_LAUNCHES))
         self.FRACTIONS = tuple(float(f) for f in os.environ.get("ARCVAE_BPTT_CHUNKS", default).split(","))
         self.S = T + 2 * (L - 1)  # launches of the BPTT wavefront (csrc/lstm.hip)
         self._wx = _layer_ptrs(enc, L, "Wx", skip0=True)
@@ -705,6 +721,11 @@ class EncoderBackwardPlan:
             # opt-in: the last chunk's GEMMs run behind the sweep, so the 128-row split tile could be resident -- measured
             # slower (1.072 vs 1.028 ms: three concurrent launches of one-block-per-CU kernels serialise in the tail)
             parts |= 64
+        elif self.quiet:
+            # beside the one-row-group persistent sweep: the split-bf16 products from LDS-staged 128 x 128 tiles
+            # (csrc/gemm.hip wgrad_quiet_kernel) -- fewer bytes and load instructions in the memory queues of the CUs
+            # the sweep's exchange ends on.  ARCVAE_WGRAD_QUIET=0: the LDS-free split kernel.
+            parts |= _lib.WGRAD_QUIET
         call("arcvae_enc_lstm_wgrad", ptr(ws.x_tb), ptr(enc.p("embedding.weight")), ptr(enc.p("lstm_layer_0.Wx")),
              ptr(ws.hseq), ptr(ws.dG), ptr(table if table is not None else ws.dtable0), ptr(ws.onehot),
              ptr(enc.g("embedding.weight")), self._dwx[0],
@@ -803,7 +824,10 @@ def _encoder_backward_gated(plan: EncoderBackwardPlan, ws: Workspace, aux, aux2,
     # (round 3: also with the mid-batch step kernels from 256 rows per GPU on -- bs 256: 3.081 -> 3.042 ms, bs 512: 6.47 -> 6.27;
     # no difference at 160 / 192 rows)
     mid_batch = ws is not None and ws.B >= 256 and not (_lib.load().arcvae_enc_lstm_tiled_for(ws.B, plan.d.H, plan.d.L, _lstm_flags(ws)) & 2)
-    wx_on_side = table_on_side and os.environ.get("ARCVAE_WX_ON_SIDE", "1" if (plan.persistent or mid_batch) else "0") != "0"
+    # (the quiet kernel reads every operand byte once per 128 x 128 tile and sizes ONE launch to the CUs: all problems of a
+    # range in one launch on aux measure faster than two launches in flight -- profiles/wgrad_quiet_step_ab.txt)
+    two_launches = (plan.persistent and not getattr(plan, "quiet", False)) or mid_batch
+    wx_on_side = table_on_side and os.environ.get("ARCVAE_WX_ON_SIDE", "1" if two_launches else "0") != "0"
     # Round 2: the token-table path is linear, so every chunk folds its OWN table (zero, one-hot GEMM, fold: first = last
     # = True) -- and the LAST chunk's, the only one in the exposed tail, is formed by main itself right behind the sweep
     # (main is idle there and needs no gate for its own sweep), in parallel with the last dWx on side and dWh on aux:

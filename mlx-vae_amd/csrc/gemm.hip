@@ -828,6 +828,227 @@ int launch_split_tn_group(int n, const SplitTN* probs, bool wide, bool one, hipS
     return arcvae_launch_status();
 }
 
+// ---- the "quiet" form of the split-bf16 TN GEMM (ARCVAE_GEMM_QUIET) ---------------------------------------------------------
+// Same arithmetic as split_tn_body (three bf16 pieces per f32 operand, the six products of weight >= 2^-16, small terms first,
+// f32 accumulate, split-K with float atomics, the column-sum rider), another way to the matrix pipe: the kernel above issues
+// 24 load instructions for 8 KB per wave and K = 16 step and no byte is shared between the waves of a block.
+// Here the four waves of a block work on the SAME k range of a 128 x 128 output tile (2 x 2 waves of 64 x 64): the two
+// [16 k][128] f32 operand tiles of a K step (16 KB) are staged ONCE in LDS by 16 LDS-DMA wave-instructions of 1 KB (four
+// per wave) and shared -- a quarter of the bytes per product and a sixth of the load instructions per byte.  Measured beside
+// the bs-64 BPTT sweep (profiles/wgrad_quiet_*.txt): one launch per chunk instead of two, the default step
+// 0.926 -> 0.910 ms; the sweep's tick beside the kernel is still ~3.7 us against 2.5 alone.
+// Ring of three stages, one barrier per K step: a wave waits for its own four DMAs of step s (counted: step s + 1 stays in
+// flight), the barrier makes that true for all four waves, the stage is read behind the barrier and re-filled one barrier
+// after its last read (for step s + 2).
+// LDS image of a stage: [A | B][16 k][128 floats], lane-linear (a DMA instruction covers two k rows); a lane FETCHES the
+// 16-byte group (lane & 31) ^ 8 in the rows k = 8 .. 15, so that the two k-halves of a wave's fragment read (lanes 0-31:
+// k = kk, lanes 32-63: k = 8 + kk, the same 32 columns) fall on the two halves of the 64 banks.  A rows are interleaved as in
+// the kernel above (MFMA tile i holds rows 2 r + i: one 8-byte LDS read per k), B columns stay natural (full 128-B
+// segments per atomic instruction of the epilogue).
+// Ragged shapes: the DMA cannot zero-fill, so its SOURCE is clamped into the operand (row min(k, K - 1), column group
+// min(m, M - 4)).  What a clamped column holds reaches only rows / columns of the product that are never stored; the rows
+// k >= kend of the last step are zeroed in registers before they are split.
+constexpr int QT_STAGES = 3, QT_TILE = 16 * 128 * 4, QT_STAGE = 2 * QT_TILE;
+
+// (amdgpu_num_vgpr: with it the compiler allocates ONE unified file for the kernel -- 200 registers, no AGPRs -- which is what
+// has to fit beside a sweep wave on a SIMD: 200 + 296 <= 512; profiles/wgrad_quiet_resource_usage.txt)
+__global__ __launch_bounds__(256) __attribute__((amdgpu_num_vgpr(128))) void wgrad_quiet_kernel(SplitTNGroup g) {
+    __shared__ __attribute__((aligned(16))) char qt_smem[QT_STAGES * QT_STAGE];
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), r = lane & 31, h = lane >> 5;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int bx = blockIdx.x, by = blockIdx.y, bz = blockIdx.z;
+    int pi = 0;
+    while (pi + 1 < g.n && bz >= g.zoff[pi + 1]) ++pi;
+    // the problem's fields once, into scalar registers (nothing but LDS-DMA may use the vector memory counter inside the K loop)
+    const SplitTN& q = g.p[pi];
+    const float* const A = q.A;
+    const float* const Bp = q.B;
+    float* const Cp = q.C;
+    float* const colsum = q.colsum;
+    const int M = q.M, N = q.N, K = q.K, lda = q.lda, ldb = q.ldb, ldc = q.ldc;
+    const int m0 = by * 128, n0 = bx * 128;
+    const int kbeg = (bz - g.zoff[pi]) * q.kchunk, kend = min(K, kbeg + q.kchunk);
+    if (m0 >= M || n0 >= N || kbeg >= kend) return;                       // block-uniform, ahead of every barrier
+    const int ns = (kend - kbeg + 15) >> 4;
+
+    // loader: wave w moves rows 4w .. 4w+3 of both tiles, two 1 KB instructions per tile: ALWAYS four per wave and stage
+    // (the counted waits below rely on it)
+    const int lrow = lane >> 5, lgrp = lane & 31;
+    auto issue = [&](int s, int stage) {
+#pragma unroll
+        for (int op = 0; op < 2; ++op)
+#pragma unroll
+            for (int u = 0; u < 2; ++u) {
+                const int kr = 4 * wave + 2 * u + lrow;                                   // row of the K step
+                const int k = min(kbeg + 16 * s + kr, K - 1);
+                const int grp = lgrp ^ (((kr >> 3) & 1) << 3);
+                const float* src = op ? Bp + (long)k * ldb + min(n0 + 4 * grp, N - 4)
+                                      : A + (long)k * lda + min(m0 + 4 * grp, M - 4);
+                const unsigned dst = __builtin_amdgcn_readfirstlane(
+                    (unsigned)(size_t)(__attribute__((address_space(3))) char*)(qt_smem + stage * QT_STAGE + op * QT_TILE + (4 * wave + 2 * u) * 512));
+                unsigned keep;
+                // (as assembly, like wgrad_planes_kernel: for the builtin the compiler drains the whole LDS-DMA queue in front
+                // of the first LDS read that might alias it; the counted waits below are the ordering)
+                asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0"
+                             : "=&s"(keep) : "v"(src), "s"(dst) : "memory");
+            }
+    };
+
+    // Two accumulators per tile: `acc` takes the hi.hi product, `acc2` the five small ones (2^-8 and less of it).  In ONE
+    // accumulator every product's result is rounded at the running sum's magnitude, six times per K step along the whole K
+    // slice of the block (measured on the test shapes: 0.204 of the element-wise parity bound against 0.067 with two).
+    f32x16 acc[2][2], acc2[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int e = 0; e < 16; ++e) { acc[i][j][e] = 0.f; acc2[i][j][e] = 0.f; }
+    const bool do_cs = colsum != nullptr && bx == 0 && wn == 0;   // wave-uniform
+    float csum[2] = {0.f, 0.f};
+    // my fragment columns inside a stage row (floats), swizzled like the fetch: rows 8 h + kk
+    const int acol = (64 * wm + 2 * r) ^ (h << 5);
+    const int bcol0 = (64 * wn + r) ^ (h << 5), bcol1 = (64 * wn + 32 + r) ^ (h << 5);
+
+    struct Pieces { u32x4_g ah[2], am[2], al[2], bh[2], bm[2], bl[2]; };
+    int cur = 0;
+    // step s: wait for its stage, re-fill the stage read at s - 1 with step s + 2, read my raw fragments (rows k >= kend zeroed)
+    auto fetch = [&](int s, float (&ra)[8][2], float (&rb)[8][2]) {
+        if (s + 1 < ns) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+        // every fragment read of step s - 1 has returned before this wave arrives (its stage is re-filled right behind the barrier)
+        asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
+        __builtin_amdgcn_s_barrier();
+        asm volatile("" ::: "memory");
+        if (s + 2 < ns) issue(s + 2, cur == 0 ? 2 : cur - 1);
+        const float* sa = reinterpret_cast<const float*>(qt_smem + cur * QT_STAGE) + (8 * h) * 128;
+        const float* sb = sa + QT_TILE / 4;
+#pragma unroll
+        for (int kk = 0; kk < 8; ++kk) {
+            const float2 v = *reinterpret_cast<const float2*>(sa + kk * 128 + acol);
+            ra[kk][0] = v.x; ra[kk][1] = v.y;
+            rb[kk][0] = sb[kk * 128 + bcol0];
+            rb[kk][1] = sb[kk * 128 + bcol1];
+        }
+        const int kv = kend - (kbeg + 16 * s) - 8 * h;     // my rows kk < kv exist
+        if (kend - (kbeg + 16 * s) < 16) {                 // block-uniform: the last, ragged step
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk)
+                if (kk >= kv) { ra[kk][0] = 0.f; ra[kk][1] = 0.f; rb[kk][0] = 0.f; rb[kk][1] = 0.f; }
+        }
+        if (do_cs) {
+#pragma unroll
+            for (int kk = 0; kk < 8; ++kk) { csum[0] += ra[kk][0]; csum[1] += ra[kk][1]; }
+        }
+        cur = cur == 2 ? 0 : cur + 1;
+    };
+    // (tile-major: the pieces of A tile 0 and B tile 0 are complete first, then B tile 1, then A tile 1 -- the order `products` needs them in)
+    auto split = [&](const float (&ra)[8][2], const float (&rb)[8][2], Pieces& P) {
+#pragma unroll
+        for (int o = 0; o < 4; ++o)
+#pragma unroll
+            for (int d = 0; d < 4; ++d) {
+                unsigned x, y, z;
+                if (o == 0 || o == 3) {
+                    const int i = o == 0 ? 0 : 1;
+                    split3(ra[2 * d][i], ra[2 * d + 1][i], x, y, z);
+                    P.ah[i][d] = x; P.am[i][d] = y; P.al[i][d] = z;
+                } else {
+                    const int j = o - 1;
+                    split3(rb[2 * d][j], rb[2 * d + 1][j], x, y, z);
+                    P.bh[j][d] = x; P.bm[j][d] = y; P.bl[j][d] = z;
+                }
+            }
+    };
+    auto products = [&](const Pieces& P) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i)
+#pragma unroll
+            for (int j = 0; j < 2; ++j) {
+                const bf16x8_t AH = __builtin_bit_cast(bf16x8_t, P.ah[i]), AM = __builtin_bit_cast(bf16x8_t, P.am[i]),
+                               AL = __builtin_bit_cast(bf16x8_t, P.al[i]);
+                const bf16x8_t BH = __builtin_bit_cast(bf16x8_t, P.bh[j]), BM_ = __builtin_bit_cast(bf16x8_t, P.bm[j]),
+                               BL = __builtin_bit_cast(bf16x8_t, P.bl[j]);
+                f32x16 c = acc2[i][j];                // small terms first
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AL, BH, c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, BL, c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AM, BM_, c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AM, BH, c, 0, 0, 0);
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, BM_, c, 0, 0, 0);
+                acc2[i][j] = c;
+                c = acc[i][j];
+                c = __builtin_amdgcn_mfma_f32_32x32x16_bf16(AH, BH, c, 0, 0, 0);
+                acc[i][j] = c;
+            }
+    };
+    issue(0, 0);
+    if (ns > 1) issue(1, 1);
+    for (int s = 0; s < ns; ++s) {
+        float ra[8][2], rb[8][2];
+        Pieces P;
+        fetch(s, ra, rb);
+        split(ra, rb, P);
+        products(P);
+        // the order asked of the scheduler: the splits of A tile 0 and B tile 0, then the products of tile (0, 0) over the
+        // split of B tile 1, those of (0, 1) over the split of A tile 1, then the other twelve
+        __builtin_amdgcn_sched_group_barrier(0x002, 96, 0);
+#pragma unroll
+        for (int e = 0; e < 12; ++e) {
+            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0); __builtin_amdgcn_sched_group_barrier(0x002, 8, 0);
+        }
+        __builtin_amdgcn_sched_group_barrier(0x008, 12, 0);
+    }
+    const int am = m0 + 64 * wm + 2 * r;                   // my two rows of C (columns of the stored A)
+    if (do_cs) {
+#pragma unroll
+        for (int i = 0; i < 2; ++i) {
+            const float v = csum[i] + __shfl_xor(csum[i], 32);
+            if (h == 0 && am + i < M) atomicAdd(colsum + am + i, v);
+        }
+    }
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j) {
+            const int n = n0 + 64 * wn + 32 * j + r;
+            if (n >= N) continue;
+#pragma unroll
+            for (int e = 0; e < 16; ++e) {
+                const int m = m0 + 64 * wm + 2 * ((e & 3) + 8 * (e >> 2) + 4 * h) + i;   // MFMA row -> interleaved row
+                if (m < M) atomicAdd(Cp + (long)m * ldc + n, acc2[i][j][e] + acc[i][j][e]);
+            }
+        }
+}
+
+// ARCVAE_GEMM_QUIET / arcvae_gemm_tn_group_accum allow_split bit 4: what the 16-byte LDS-DMA needs of BOTH operands
+inline bool quiet_tn_ok(int M, int N, const float* A, int lda, const float* B, int ldb) {
+    return split_tn_ok(M, N, A, lda, B, ldb) && (N % 4) == 0 && (ldb % 4) == 0 && (reinterpret_cast<uintptr_t>(B) & 15) == 0;
+}
+// n problems in one launch; the K slices (multiples of 16, at least 256 of K where K allows) walk blockIdx.z.  The grid is
+// sized to stay at or under ARCVAE_SPLIT_BLOCKS: beside a sweep one block fits per CU, and a second round would wait for the first.
+int launch_quiet_tn_group(int n, const SplitTN* probs, hipStream_t stream) {
+    SplitTNGroup g;
+    g.n = n;
+    int Mmax = 0, Nmax = 0, ztot = 0, tiles = 0;
+    static const int target = arcvae_env_int("ARCVAE_SPLIT_BLOCKS", 256);
+    for (int i = 0; i < n; ++i) {
+        g.p[i] = probs[i];
+        Mmax = max(Mmax, probs[i].M); Nmax = max(Nmax, probs[i].N);
+        tiles += ceil_div(probs[i].M, 128) * ceil_div(probs[i].N, 128);
+    }
+    for (int i = 0; i < n; ++i) {
+        SplitTN& p = g.p[i];
+        const int z = max(1, min(target / max(1, tiles), p.K / 256));
+        p.kchunk = ceil_div(ceil_div(p.K, z), 16) * 16;
+        g.zoff[i] = ztot;
+        ztot += ceil_div(p.K, p.kchunk);
+    }
+    g.zoff[n] = ztot;
+    for (int i = n; i < ARCVAE_SPLIT_GROUP_MAX; ++i) { g.p[i] = g.p[0]; g.zoff[i + 1] = ztot; }
+    hipLaunchKernelGGL(wgrad_quiet_kernel, dim3(ceil_div(Nmax, 128), ceil_div(Mmax, 128), ztot), dim3(256), 0, stream, g);
+    return arcvae_launch_status();
+}
+
 // ---- throughput mode: weight gradients from OCTET-MAJOR bf16 copies ------------------------------------------------------
 // C[M,N] += A^T . B where the sweeps' epilogues have left bf16 copies of both operands in the layout an MFMA fragment is
 // loaded in: X_oct[k / 8][row][k % 8] (k = t * B + b, the contraction index; row = gate column or hidden unit), so a
@@ -993,6 +1214,17 @@ extern "C" int arcvae_gemm_f32(int transA, int transB, int M, int N, int K,
     // below beats the LDS-free split kernel's one-product form, which is bound by its operand loads (207 vs 97 TFLOP/s on
     // the [2048 x 512] x K = 65536 weight gradients of BASELINE.json configs[2])
     const bool bf16_tile_tn = (flags & ARCVAE_GEMM_BF16) && M >= 256 && N >= 256 && K >= 2048;
+    // ARCVAE_GEMM_QUIET: the LDS-staged form of the split-bf16 TN "+=" kernel, and nothing else (no other kernel is chosen
+    // in its place: operands it cannot take are an argument error)
+    if (flags & ARCVAE_GEMM_QUIET) {
+        if (!(transA && !transB && (flags & ARCVAE_GEMM_ACCUMULATE) && (flags & ARCVAE_GEMM_SPLITK)) || bias || p.act != 0 ||
+            (flags & (ARCVAE_GEMM_TILE64 | ARCVAE_GEMM_TILE128 | ARCVAE_GEMM_TILE_WIDE | ARCVAE_GEMM_BF16 | ARCVAE_GEMM_SPLIT3)) ||
+            !quiet_tn_ok(M, N, A, lda, B, ldb))
+            return ARCVAE_ERR_ARG;
+        SplitTN q;
+        q.A = A; q.B = B; q.C = C; q.colsum = nullptr; q.M = M; q.N = N; q.K = K; q.lda = lda; q.ldb = ldb; q.ldc = ldc; q.kchunk = 0;
+        return launch_quiet_tn_group(1, &q, stream);
+    }
     // TN "+=" with split-K allowed (weight-gradient / token-table shapes): split-bf16 kernel
     if (!bf16_tile_tn)
     if (transA && !transB && (flags & ARCVAE_GEMM_ACCUMULATE) && (flags & ARCVAE_GEMM_SPLITK) && !bias && p.act == 0 &&
@@ -1152,7 +1384,11 @@ int arcvae_gemm_tn_group_accum(int n, int M, int N, const int* K, const float* c
                 q[i].A = A[i]; q[i].B = B[i]; q[i].C = C[i]; q[i].colsum = (colsum && ride) ? colsum[i] : nullptr; q[i].M = M; q[i].N = N; q[i].K = K[i];
                 q[i].lda = lda; q[i].ldb = ldb; q[i].ldc = ldc; q[i].kchunk = 0;
             }
-            const int rc = launch_split_tn_group(n, q, (allow_split & 2) != 0, (allow_split & 4) != 0, stream);
+            // bit 4 = the LDS-staged "quiet" form (wgrad_quiet_kernel) where both operands allow 16-byte LDS-DMA; not with bits 1 / 2
+            bool quiet = (allow_split & 16) != 0 && !(allow_split & 6);
+            for (int i = 0; i < n; ++i) quiet = quiet && quiet_tn_ok(M, N, A[i], lda, B[i], ldb);
+            const int rc = quiet ? launch_quiet_tn_group(n, q, stream)
+                                 : launch_split_tn_group(n, q, (allow_split & 2) != 0, (allow_split & 4) != 0, stream);
             if (rc || ride) return rc;
             return colsums_by_launch();
         }

@@ -3939,6 +3939,9 @@ extern "C" int arcvae_dense_stack_backward(const float* gates, const float* dh_t
 //   runs behind the sweep: no sweep block is resident, the 322-register tile fits);
 //   bit 4 = exact-f32 MFMA tile GEMMs instead of the split-bf16 kernel (45 instead of 208 registers per lane: what
 //   fits on a SIMD beside a persistent sweep wave of more than 296 registers, i.e. the 2 / 4 row-group sweeps)
+//   bit 9 = the split-bf16 per-layer GEMMs on their LDS-staged "quiet" form (gemm.hip: wgrad_quiet_kernel; one launch
+//   carries every problem of the range) -- for ranges that run beside the one-row-group persistent sweep; the token-table
+//   GEMM keeps its kernel
 //   bit 11 = h_oct / dG_oct are the three-plane operand rings hseq_t / dG_t with all T slots: GEMMs from the planes
 //   bit 12 (with 11) = those rings are scratch: this call first splits dG / h of its time range into them (mid-size batches)
 //   onehot_ws [T*B, roundup(V,4)] workspace: one-hot token rows, written when `first` != 0 (token-table part)
@@ -4049,7 +4052,8 @@ extern "C" int arcvae_enc_lstm_wgrad(const int32_t* x_tb, const float* emb, cons
             } else
             for (int i = 0; i < n; i += 8) {
                 rc = arcvae_gemm_tn_group_accum(n - i < 8 ? n - i : 8, G, H, Kg + i, Ag + i, G, Bg + i, H, Cg + i, H,
-                                                (parts & 1024) ? 8 : (exact_f32 ? 0 : (1 | (wide ? 2 : 0) | (b16 ? 4 : 0))), Sg + i, stream);
+                                                (parts & 1024) ? 8 : (exact_f32 ? 0 : (1 | (wide ? 2 : 0) | (b16 ? 4 : 0) | ((parts & 512) ? 16 : 0))),
+                                                Sg + i, stream);
                 if (rc) return rc;       // (bias gradients dbias_l += colsum(dG_l): inside the split kernel, else by launch)
             }
         }

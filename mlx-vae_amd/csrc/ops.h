@@ -5,6 +5,8 @@
 #include "common.h"
 
 // internal (C++ linkage): grouped weight-gradient GEMMs, see gemm.hip
+// allow_split: bit 0 = split-bf16 kernel, bit 1 = its 128-row tile, bit 2 = one bf16 product (throughput mode), bit 3 = three-piece
+// tile GEMM, bit 4 (with bit 0 alone) = the LDS-staged quiet form of the split-bf16 kernel (ARCVAE_GEMM_QUIET)
 int arcvae_gemm_tn_group_accum(int n, int M, int N, const int* K, const float* const* A, int lda,
                                const float* const* B, int ldb, float* const* C, int ldc, int allow_split,
                                float* const* colsum /* optional: colsum_i[M] += column sums of A_i */, hipStream_t stream);
