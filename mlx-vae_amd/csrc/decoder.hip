@@ -71,9 +71,10 @@ __global__ __launch_bounds__(256) void cell_zero_fwd_kernel(const float* __restr
 }
 
 // dG (pre-activation gradients; forget-gate columns are exactly 0) from dh and the saved pre-activations.
+// write_f = 0: the forget quarter is not stored (its readers skip it: dead_gate_skip below).
 __global__ __launch_bounds__(256) void cell_zero_bwd_kernel(const float* __restrict__ G,
                                                             const float* __restrict__ dh, float* dG, long R,
-                                                            int H) {
+                                                            int H, int write_f) {
     const long idx = (long)blockIdx.x * blockDim.x + threadIdx.x;
     if (idx >= R * H) return;
     const int unit = (int)(idx % H);
@@ -85,7 +86,7 @@ __global__ __launch_bounds__(256) void cell_zero_bwd_kernel(const float* __restr
     const float dc = d * o * (1.f - tc * tc);
     float* o4 = dG + r * 4 * H + unit;
     o4[0] = dc * g * i * (1.f - i);
-    o4[H] = 0.f;
+    if (write_f) o4[H] = 0.f;
     o4[2 * H] = dc * i * (1.f - g * g);
     o4[3 * H] = d * tc * o * (1.f - o);
 }
@@ -399,6 +400,13 @@ __global__ __launch_bounds__(256) void dec_sample_categorical_kernel(const float
 
 inline int blocks_for(long n) { return (int)((n + 255) / 256); }
 
+// Layers l >= 1: the zero-state cell never reads the forget gate (c = i * g), so a quarter of G_l = h . Wx_l^T + b, of
+// dWx_l += dG^T . h, of dbias_l and of dh = dG . Wx_l is spent on columns that are discarded or exactly zero.  With H % 64 == 0
+// the GEMMs step over [H, 2H) of their 4H-wide operands as a gap (ops.h arcvae_gemm_f32_gap): `gpre` and `dG` keep their
+// [R, 4H] layout, the forget quarter of both is neither written nor read, and the forget rows of dWx_l / dbias_l are not
+// touched ("+= 0").  Decided once per call; ARCVAE_DEC_SKIP_F=0 restores the full-width products (A/B runs, equality tests).
+inline bool dead_gate_skip(int H) { return (H % 64) == 0 && arcvae_env_int("ARCVAE_DEC_SKIP_F", 1) != 0; }
+
 }  // namespace
 
 // Dense decoder forward.  Pointer arrays Wx/bias are HOST arrays [L] of device pointers.
@@ -424,6 +432,7 @@ extern "C" int arcvae_dec_forward_dense(const float* emb, const float* const* Wx
         if (!Wx[l] || !bias[l]) return ARCVAE_ERR_ARG;
     const int G = 4 * H;
     const long R = (long)B * V;
+    const bool skipf = dead_gate_skip(H);
     int rc = ARCVAE_OK;
     if (!tail_only) {
         rc = arcvae_gemm_f32(0, 1, V, G, E, emb, E, Wx[0], E + C, tableD, G, nullptr, 0, stream);
@@ -436,10 +445,13 @@ extern "C" int arcvae_dec_forward_dense(const float* emb, const float* const* Wx
         float* Gl = gpre + (long)(l - 1) * R * G;
         if (no_gpre && R >= 4096 &&
             arcvae_gemm_cell_zero((int)R, H, H, hact + (long)(l - 1) * R * H, H, Wx[l], H, bias[l], hact + (long)l * R * H,
-                                  stream) == ARCVAE_OK)
+                                  arcvae_env_int("ARCVAE_DEC_SKIP_F", 1) != 0, stream) == ARCVAE_OK)
             continue;                                      // (the pre-activations of this layer were never written)
-        rc = arcvae_gemm_f32(0, 1, (int)R, G, H, hact + (long)(l - 1) * R * H, H, Wx[l], H, Gl, G, bias[l], BF,
-                             stream);
+        if (skipf)   // a gap in N: the rows of Wx_l, the entries of bias_l and the columns of G_l
+            rc = arcvae_gemm_f32_gap(0, 1, (int)R, 3 * H, H, hact + (long)(l - 1) * R * H, H, Wx[l], H, Gl, G, bias[l], BF, 2, H, H,
+                                     nullptr, stream);
+        else
+            rc = arcvae_gemm_f32(0, 1, (int)R, G, H, hact + (long)(l - 1) * R * H, H, Wx[l], H, Gl, G, bias[l], BF, stream);
         if (rc) return rc;
         hipLaunchKernelGGL(cell_zero_fwd_kernel, dim3(blocks_for(R * H)), dim3(256), 0, stream, Gl,
                            hact + (long)l * R * H, R, H);
@@ -527,6 +539,7 @@ extern "C" int arcvae_dec_backward_dense(const float* emb, const float* const* W
     const int G = 4 * H;
     const long R = (long)B * V;
     const int Ri = (int)R;
+    const bool skipf = dead_gate_skip(H);
     const int BF = (flags & ARCVAE_DEC_BF16) ? ARCVAE_GEMM_BF16 : ((flags & ARCVAE_DEC_SPLIT3) ? ARCVAE_GEMM_SPLIT3 : 0);
     const int SK = ARCVAE_GEMM_ACCUMULATE | ARCVAE_GEMM_SPLITK | (BF & ARCVAE_GEMM_BF16);   // (TN "+=": the split TN kernel either way)
     // ARCVAE_DEC_PART_TAIL: only fc_out's gradients and dh_top = dlogits . Wout (into dh[0 .. R*H)); ARCVAE_DEC_PART_HEAD: only
@@ -538,9 +551,13 @@ extern "C" int arcvae_dec_backward_dense(const float* emb, const float* const* W
     const float* hTop = hact + (long)(L - 1) * R * H;
     int rc = ARCVAE_OK;
     if (!head_only) {
-        rc = arcvae_gemm_f32(1, 0, V, H, Ri, dlogits, V, hTop, H, dWout, H, nullptr, SK, stream);  // dWout += dL^T h
-        if (rc) return rc;
-        rc = arcvae_colsum_accum(dlogits, Ri, V, V, dbout, 1.0f, stream);
+        if (skipf) {   // dWout += dL^T h, and dbout += colsum(dL) as the split TN kernel's rider (by a colsum launch where another kernel is chosen)
+            rc = arcvae_gemm_f32_gap(1, 0, V, H, Ri, dlogits, V, hTop, H, dWout, H, nullptr, SK, 0, 0, 0, dbout, stream);
+        } else {
+            rc = arcvae_gemm_f32(1, 0, V, H, Ri, dlogits, V, hTop, H, dWout, H, nullptr, SK, stream);
+            if (rc) return rc;
+            rc = arcvae_colsum_accum(dlogits, Ri, V, V, dbout, 1.0f, stream);
+        }
         if (rc) return rc;
         rc = arcvae_gemm_f32(0, 0, Ri, H, V, dlogits, V, Wout, H, dhA, H, nullptr, BF, stream);  // dh = dL Wout
         if (rc) return rc;
@@ -548,13 +565,23 @@ extern "C" int arcvae_dec_backward_dense(const float* emb, const float* const* W
     }
     for (int l = L - 1; l >= 1 && !head_only; --l) {
         const float* Gl = gpre + (long)(l - 1) * R * G;
-        hipLaunchKernelGGL(cell_zero_bwd_kernel, dim3(blocks_for(R * H)), dim3(256), 0, stream, Gl, dhA, dG, R, H);
-        rc = arcvae_gemm_f32(1, 0, G, H, Ri, dG, G, hact + (long)(l - 1) * R * H, H, dWx[l], H, nullptr, SK, stream);
-        if (rc) return rc;
-        rc = arcvae_colsum_accum(dG, Ri, G, G, dbias[l], 1.0f, stream);
-        if (rc) return rc;
-        rc = arcvae_gemm_f32(0, 0, Ri, H, G, dG, G, Wx[l], H, dhB, H, nullptr, BF, stream);  // dh_{l-1} = dG Wx_l
-        if (rc) return rc;
+        hipLaunchKernelGGL(cell_zero_bwd_kernel, dim3(blocks_for(R * H)), dim3(256), 0, stream, Gl, dhA, dG, R, H, skipf ? 0 : 1);
+        if (skipf) {
+            // dWx_l += dG^T h_{l-1} with a gap in M (the columns of dG, the rows of dWx_l) and dbias_l as the launch's rider;
+            // dh_{l-1} = dG Wx_l with a gap in K (the columns of dG, the rows of Wx_l)
+            rc = arcvae_gemm_f32_gap(1, 0, 3 * H, H, Ri, dG, G, hact + (long)(l - 1) * R * H, H, dWx[l], H, nullptr, SK, 1, H, H,
+                                     dbias[l], stream);
+            if (rc) return rc;
+            rc = arcvae_gemm_f32_gap(0, 0, Ri, H, 3 * H, dG, G, Wx[l], H, dhB, H, nullptr, BF, 3, H, H, nullptr, stream);
+            if (rc) return rc;
+        } else {
+            rc = arcvae_gemm_f32(1, 0, G, H, Ri, dG, G, hact + (long)(l - 1) * R * H, H, dWx[l], H, nullptr, SK, stream);
+            if (rc) return rc;
+            rc = arcvae_colsum_accum(dG, Ri, G, G, dbias[l], 1.0f, stream);
+            if (rc) return rc;
+            rc = arcvae_gemm_f32(0, 0, Ri, H, G, dG, G, Wx[l], H, dhB, H, nullptr, BF, stream);  // dh_{l-1} = dG Wx_l
+            if (rc) return rc;
+        }
         float* t = dhA; dhA = dhB; dhB = t;
     }
     hipLaunchKernelGGL(dec_l0_bwd_kernel, dim3(ceil_div(H, 64), V), dim3(256), 0, stream, tableD, cond, Wx[0],

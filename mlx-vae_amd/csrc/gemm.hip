@@ -52,7 +52,13 @@ struct GemmP {
     int accumulate;  // C += result (non-split path)
     int act;         // 0 none, 1 tanh, 2 d-tanh: C = acc * (1 - T^2) with T = `bias` read as an [M,ldc] matrix
     int kchunk;      // K range per blockIdx.z (multiple of 16)
+    // A gap in ONE dimension (gap_dim: 0 none, 1 M, 2 N, 3 K; gap_at, gap_len multiples of 64): M / N / K above are the LOGICAL
+    // extents, and a tile (block tile in M or N, K tile in K) whose logical offset is >= gap_at addresses physical offset + gap_len
+    // in every operand, the bias and C.  The dense decoder skips the dead forget-gate quarter [H, 2H) of its [.., 4H] arrays
+    // this way: no repacked weights, no extra pass, the k order of every output element unchanged.
+    int gap_dim = 0, gap_at = 0, gap_len = 0;
 };
+__device__ __forceinline__ int gap_off(const GemmP& p, int dim, int at) { return (p.gap_dim == dim && at >= p.gap_at) ? p.gap_len : 0; }
 
 constexpr int BK = 16;
 constexpr int PAD = 4;
@@ -135,7 +141,9 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, const int bx, con
 
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int m0 = by * BM, n0 = bx * BN;
+    const int moff = gap_off(p, 1, by * BM), noff = gap_off(p, 2, bx * BN);
+    const int m0 = by * BM + moff, n0 = bx * BN + noff;      // physical; so are Mp, Np (the tile's own side of the gap)
+    const int Mp = p.M + moff, Np = p.N + noff;
     const int kbeg = bz * p.kchunk;
     const int kend = min(p.K, kbeg + p.kchunk);
 
@@ -151,8 +159,9 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, const int bx, con
     TileLoader<BN, BKC, VB> lb;
     const int nk = (kend - kbeg + BK - 1) / BK;
     if (nk > 0) {
-        la.load(p.A, p.lda, m0, p.M, kbeg, kend, tid);
-        lb.load(p.B, p.ldb, n0, p.N, kbeg, kend, tid);
+        const int ko = gap_off(p, 3, kbeg);
+        la.load(p.A, p.lda, m0, Mp, kbeg + ko, kend + ko, tid);
+        lb.load(p.B, p.ldb, n0, Np, kbeg + ko, kend + ko, tid);
         la.store(As0, tid);
         lb.store(Bs0, tid);
     }
@@ -160,8 +169,9 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, const int bx, con
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
         if (kt + 1 < nk) {
-            la.load(p.A, p.lda, m0, p.M, kbeg + (kt + 1) * BK, kend, tid);
-            lb.load(p.B, p.ldb, n0, p.N, kbeg + (kt + 1) * BK, kend, tid);
+            const int kn = kbeg + (kt + 1) * BK, ko = gap_off(p, 3, kn);
+            la.load(p.A, p.lda, m0, Mp, kn + ko, kend + ko, tid);
+            lb.load(p.B, p.ldb, n0, Np, kn + ko, kend + ko, tid);
         }
         const float* as = As0 + cur * BK * LDA_S + (lane >> 5) * LDA_S + wm * WM + (lane & 31);
         const float* bs = Bs0 + cur * BK * LDB_S + (lane >> 5) * LDB_S + wn * WN + (lane & 31);
@@ -190,12 +200,12 @@ __device__ __forceinline__ void gemm_tile_body(const GemmP& p, const int bx, con
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int col = n0 + wn * WN + j * 32 + (lane & 31);
-            if (col >= p.N) continue;
+            if (col >= Np) continue;
             const float bv = (p.bias && p.act != 2 && bz == 0) ? p.bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (row >= p.M) continue;
+                if (row >= Mp) continue;
                 float* c = p.C + (long)row * p.ldc + col;
                 float v = acc[i][j][r] + bv;
                 if (split) {
@@ -316,7 +326,9 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmP& p, const int bx, con
     __bf16* const Bs0 = smem + 2 * PIECES * IA;     // Bs[buf][piece] = Bs0 + (buf * PIECES + piece) * IB
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
     const int wm = wave >> 1, wn = wave & 1;
-    const int m0 = by * BM, n0 = bx * BN;
+    const int moff = gap_off(p, 1, by * BM), noff = gap_off(p, 2, bx * BN);
+    const int m0 = by * BM + moff, n0 = bx * BN + noff;      // physical; so are Mp, Np (the tile's own side of the gap)
+    const int Mp = p.M + moff, Np = p.N + noff;
     const int kbeg = bz * p.kchunk, kend = min(p.K, kbeg + p.kchunk);
     f32x16 acc[MT][NT];
 #pragma unroll
@@ -332,8 +344,9 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmP& p, const int bx, con
     BfLoader<BN, BKC, BKT> lb;
     const int nk = (kend - kbeg + BKT - 1) / BKT;
     if (nk > 0) {
-        la.load(p.A, p.lda, m0, p.M, kbeg, kend, tid);
-        lb.load(p.B, p.ldb, n0, p.N, kbeg, kend, tid);
+        const int ko = gap_off(p, 3, kbeg);
+        la.load(p.A, p.lda, m0, Mp, kbeg + ko, kend + ko, tid);
+        lb.load(p.B, p.ldb, n0, Np, kbeg + ko, kend + ko, tid);
         la.template store<PIECES>(As0, tid, IA);
         lb.template store<PIECES>(Bs0, tid, IB);
     }
@@ -341,8 +354,9 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmP& p, const int bx, con
     for (int kt = 0; kt < nk; ++kt) {
         const int cur = kt & 1;
         if (kt + 1 < nk) {
-            la.load(p.A, p.lda, m0, p.M, kbeg + (kt + 1) * BKT, kend, tid);
-            lb.load(p.B, p.ldb, n0, p.N, kbeg + (kt + 1) * BKT, kend, tid);
+            const int kn = kbeg + (kt + 1) * BKT, ko = gap_off(p, 3, kn);
+            la.load(p.A, p.lda, m0, Mp, kn + ko, kend + ko, tid);
+            lb.load(p.B, p.ldb, n0, Np, kn + ko, kend + ko, tid);
         }
         const __bf16* as = As0 + cur * PIECES * IA + (wm * WM + (lane & 31)) * LDK + 8 * (lane >> 5);
         const __bf16* bs = Bs0 + cur * PIECES * IB + (wn * WN + (lane & 31)) * LDK + 8 * (lane >> 5);
@@ -382,12 +396,12 @@ __device__ __forceinline__ void gemm_bf16_body(const GemmP& p, const int bx, con
 #pragma unroll
         for (int j = 0; j < NT; ++j) {
             const int col = n0 + wn * WN + j * 32 + (lane & 31);
-            if (col >= p.N) continue;
+            if (col >= Np) continue;
             const float bv = (p.bias && p.act != 2 && bz == 0) ? p.bias[col] : 0.f;
 #pragma unroll
             for (int r = 0; r < 16; ++r) {
                 const int row = m0 + wm * WM + i * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                if (row >= p.M) continue;
+                if (row >= Mp) continue;
                 float* c = p.C + (long)row * p.ldc + col;
                 float v = acc[i][j][r] + bv;
                 if (split) {
@@ -542,6 +556,102 @@ __global__ __launch_bounds__(256) void gemm_cell_zero_kernel(CellGemmP p) {
     }
 }
 
+// The same layer WITHOUT the dead forget gate (the zero-state cell is c = i * g: the kernel above computes a quarter of its
+// columns for nothing).  Block tile 64 rows x 192 logical columns = 64 units x (i, g, o): logical column c = 3 * unit + s reads
+// weight row gate(s) * H + unit, gate = 0, 2, 3, so a unit's three gates are neighbouring floats of a row of the pre-activation
+// image [64][193] (49 KB: three blocks per CU).  2 x 2 waves of 32 x 96 (one A fragment feeds three products).  Same loads, same
+// k order of the exact-f32 MFMAs per output element, same "+ bias", same cell arithmetic: h is bit-identical to the kernel
+// above and to the two-kernel path.  A row's 64 cells are evaluated by one wave (LDS stride 3: conflict-free) and leave as
+// one 256-byte segment; A is re-read by H / 64 column blocks instead of 4 H / 128.
+__global__ __launch_bounds__(256) void gemm_cell_zero3_kernel(CellGemmP p) {
+    constexpr int BM = 64, BN = 192, WM = 32, WN = 96, NT = 3, GS = BN + 1;
+    constexpr int LDA_S = BM + PAD, LDB_S = BN + PAD;
+    extern __shared__ __attribute__((aligned(16))) float smem[];   // max(operand tiles: 33.8 KB, pre-activation image [64][193]: 49.4 KB)
+    float* const As0 = smem;
+    float* const Bs0 = smem + 2 * BK * LDA_S;
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
+    const int wm = wave >> 1, wn = wave & 1;
+    const int m0 = blockIdx.y * BM, n0 = blockIdx.x * BN;      // n0: first LOGICAL column (3 * unit + s)
+    const int G3 = 3 * p.H;
+    f32x16 acc[NT];
+#pragma unroll
+    for (int j = 0; j < NT; ++j)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[j][r] = 0.f;
+    TileLoader<BM, true, 4> la;
+    float4 vb[3];
+    auto wrow = [&](int c) { const int u = c / 3, s = c - 3 * u; return (s + (s > 0 ? 1 : 0)) * p.H + u; };   // s = 0, 1, 2 -> gate i, g, o
+    auto load_b = [&](int k0) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int idx = tid + i * 256, c = n0 + (idx >> 2), k = k0 + (idx & 3) * 4;
+            float4 z = make_float4(0.f, 0.f, 0.f, 0.f);
+            if (c < G3 && k < p.K) z = *reinterpret_cast<const float4*>(p.W + (long)wrow(c) * p.ldw + k);
+            vb[i] = z;
+        }
+    };
+    auto store_b = [&](float* S) {
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            const int idx = tid + i * 256, r = idx >> 2, k = (idx & 3) * 4;
+            S[(k + 0) * LDB_S + r] = vb[i].x;
+            S[(k + 1) * LDB_S + r] = vb[i].y;
+            S[(k + 2) * LDB_S + r] = vb[i].z;
+            S[(k + 3) * LDB_S + r] = vb[i].w;
+        }
+    };
+    const int nk = (p.K + BK - 1) / BK;
+    la.load(p.A, p.lda, m0, p.M, 0, p.K, tid);
+    load_b(0);
+    la.store(As0, tid);
+    store_b(Bs0);
+    __syncthreads();
+    for (int kt = 0; kt < nk; ++kt) {
+        const int cur = kt & 1;
+        if (kt + 1 < nk) {
+            la.load(p.A, p.lda, m0, p.M, (kt + 1) * BK, p.K, tid);
+            load_b((kt + 1) * BK);
+        }
+        const float* as = As0 + cur * BK * LDA_S + (lane >> 5) * LDA_S + wm * WM + (lane & 31);
+        const float* bs = Bs0 + cur * BK * LDB_S + (lane >> 5) * LDB_S + wn * WN + (lane & 31);
+#pragma unroll
+        for (int kk = 0; kk < BK; kk += 2) {
+            const float a = as[kk * LDA_S];
+            float b[NT];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) b[j] = bs[kk * LDB_S + j * 32];
+#pragma unroll
+            for (int j = 0; j < NT; ++j) acc[j] = __builtin_amdgcn_mfma_f32_32x32x2f32(a, b[j], acc[j], 0, 0, 0);
+        }
+        if (kt + 1 < nk) {
+            la.store(As0 + (cur ^ 1) * BK * LDA_S, tid);
+            store_b(Bs0 + (cur ^ 1) * BK * LDB_S);
+        }
+        __syncthreads();
+    }
+    float* gs = smem;                                  // (every operand read is behind the loop's last barrier)
+#pragma unroll
+    for (int j = 0; j < NT; ++j) {
+        const int cl = wn * WN + j * 32 + (lane & 31);   // logical column within the block tile
+        const int c = n0 + cl;
+        const float bv = c < G3 ? p.bias[wrow(c)] : 0.f;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int row = wm * WM + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+            gs[row * GS + cl] = acc[j][r] + bv;
+        }
+    }
+    __syncthreads();
+    const int u = blockIdx.x * 64 + lane;              // my unit: the wave's 64 lanes hold one row's 64 units
+#pragma unroll
+    for (int q = 0; q < 16; ++q) {
+        const int row = q * 4 + wave;
+        const float* g3 = gs + row * GS + 3 * lane;
+        const float ig = sigmoidf_acc(g3[0]), gg = tanhf(g3[1]), og = sigmoidf_acc(g3[2]);
+        if (m0 + row < p.M && u < p.H) p.Hout[(long)(m0 + row) * p.H + u] = og * tanhf(ig * gg);
+    }
+}
+
 // Grouped launch: up to 8 same-layout problems in ONE launch (blockIdx.z walks [problem][k-slice]); used for the
 // per-layer weight-gradient GEMMs of a BPTT chunk, which are small, independent and otherwise each pay a launch.
 #define ARCVAE_GEMM_GROUP_MAX 8
@@ -564,19 +674,25 @@ template <bool BKC>
 __global__ __launch_bounds__(256) void gemm_skinny_kernel(GemmP p) {
     __shared__ float red[4 * 256];
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6;
-    const int m0 = blockIdx.y * 16, n0 = blockIdx.x * 16;
+    // gap (GemmP): in N the block's columns move as in the tile kernels; in K (the [K, N] form only) the waves keep their
+    // quarters of the PHYSICAL K = p.K + gap_len and pass over the 16-float chunks inside the gap -- the same partition, and
+    // so the same sum order, as the full-width product whose gap columns of A are zero
+    const int noff = gap_off(p, 2, blockIdx.x * 16), Np = p.N + noff;
+    const int m0 = blockIdx.y * 16, n0 = blockIdx.x * 16 + noff;
     const int arow = min(m0 + (lane & 15), p.M - 1);
-    const int bcol = min(n0 + (lane & 15), p.N - 1);
+    const int bcol = min(n0 + (lane & 15), Np - 1);
     f32x4 acc0 = {0.f, 0.f, 0.f, 0.f}, acc1 = {0.f, 0.f, 0.f, 0.f};
-    if constexpr (BKC)
+    if constexpr (BKC) {
         skinny_accum_kk(acc0, acc1, p.A, (long)arow * p.lda, p.B, (long)bcol * p.ldb, p.K, wave, lane);
-    else
-        skinny_accum_kn(acc0, acc1, p.A, (long)arow * p.lda, p.B, p.ldb, bcol, p.K, wave, lane);
+    } else {
+        const int kgap = p.gap_dim == 3 ? p.gap_len : 0;
+        skinny_accum_kn(acc0, acc1, p.A, (long)arow * p.lda, p.B, p.ldb, bcol, p.K + kgap, wave, lane, p.gap_at, p.gap_at + kgap);
+    }
     skinny_store_partial(red, acc0, acc1, wave, lane);
     __syncthreads();
     const int row = tid >> 4, col = tid & 15;
     const int gr = m0 + row, gc = n0 + col;
-    if (gr < p.M && gc < p.N) {
+    if (gr < p.M && gc < Np) {
         float v = skinny_reduced(red, row, col);
         if (p.bias && p.act != 2) v += p.bias[gc];
         float* c = p.C + (long)gr * p.ldc + gc;
@@ -611,6 +727,9 @@ struct SplitTN {
                       // the first column of tiles sums the values it loads anyway -- a separate column-sum launch beside the
                       // persistent sweep waited ~60 us for CU resources, profiles/r02_tail_timeline.txt)
     int M, N, K, lda, ldb, ldc, kchunk;
+    // a gap in M as in GemmP (M is the LOGICAL extent): a block tile whose first logical row is >= gap_at takes the columns of A,
+    // the rows of C and the entries of colsum gap_len further on.  gap_at: a multiple of the block tile's 32 * MI rows.
+    int gap_at = 0, gap_len = 0;
 };
 #define ARCVAE_SPLIT_GROUP_MAX 8
 struct SplitTNGroup {
@@ -630,7 +749,15 @@ struct SplitTNGroup {
 // for the sweep's chunk to end (measured: step 1.147 vs 1.083 ms).
 // ONE: plain bf16 operands (the hi piece only, one product): the throughput mode's weight-gradient GEMM.
 template <int MI, int NJ, bool ONE = false>
-__device__ __forceinline__ void split_tn_body(const SplitTN& p, const int bx, const int by, const int bz, float* red) {
+__device__ __forceinline__ void split_tn_body(const SplitTN& q, const int bx, const int by, const int bz, float* red) {
+    // the gap (block-uniform): a tile on the far side works on the operands moved by gap_len columns of A / rows of C / entries
+    // of colsum, with its logical row indices
+    SplitTN p = q;
+    if (q.gap_len && by * 32 * MI >= q.gap_at) {
+        p.A += q.gap_len;
+        p.C += (long)q.gap_len * q.ldc;
+        if (q.colsum) p.colsum += q.gap_len;
+    }
     constexpr int TT = MI * NJ;                    // 32 x 32 MFMA tiles of the block tile
     const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, r = lane & 31, h = lane >> 5;
     const int m0 = by * 32 * MI, n0 = bx * 32 * NJ;
@@ -801,11 +928,16 @@ int launch_split_tn_group(int n, const SplitTN* probs, bool wide, bool one, hipS
     // ARCVAE_SPLIT_TILE: 2 (default) = 64 x 64 tiles (fits beside a persistent sweep), 4 = 128 x 64 everywhere;
     // `wide`: the caller knows no sweep is resident (the last chunk's GEMMs run behind the sweep): 128 x 64
     static const int mi_env = arcvae_env_int("ARCVAE_SPLIT_TILE", 2) == 4 ? 4 : 2;
-    const int mi = (wide || one) ? 4 : mi_env;
+    int mi = (wide || one) ? 4 : mi_env;
+    for (int i = 0; i < n; ++i)
+        if (probs[i].gap_len && (probs[i].gap_at % 128) != 0) mi = 2;          // the gap lies on a 64-row tile boundary only
     const int tiles = ceil_div(Mmax, 32 * mi) * ceil_div(Nmax, 64);
     for (int i = 0; i < n; ++i) {
         SplitTN& p = g.p[i];
         int z = min(ceil_div(target, tiles * n), max(1, p.K / 256));           // at least 256 of K per block (4 steps a wave)
+        // (a gapped problem has 3/4 of the tiles its slicing was tuned for -- 48 instead of 64 at H 256: rounding the slice count
+        // up would give 288 blocks, a second round on 32 CUs; rounded down the launch stays one round of 240)
+        if (p.gap_len) z = min(z, max(1, target / (tiles * n)));
         z = max(1, z);
         p.kchunk = ceil_div(ceil_div(p.K, z), 64) * 64;
         z = ceil_div(p.K, p.kchunk);
@@ -816,7 +948,9 @@ int launch_split_tn_group(int n, const SplitTN* probs, bool wide, bool one, hipS
     for (int i = n; i < ARCVAE_SPLIT_GROUP_MAX; ++i) { g.p[i] = g.p[0]; g.zoff[i + 1] = ztot; }
     dim3 grid(ceil_div(Nmax, 64), ceil_div(Mmax, 32 * mi), ztot);
     const size_t lds = sizeof(float) * 2 * (mi * 2) * 16 * 64;                   // two accumulator images: 32 / 64 KB
-    if (one) {   // throughput mode: one bf16 product per step (its 128-row tile needs no operand pieces: 4 x 2 tiles always)
+    if (one && mi == 2) {
+        hipLaunchKernelGGL((gemm_split_tn_group_kernel<2, 2, true>), grid, dim3(256), lds, stream, g);
+    } else if (one) {   // throughput mode: one bf16 product per step (its 128-row tile needs no operand pieces: 4 x 2 tiles unless a gap forbids)
         (void)hipFuncSetAttribute((const void*)gemm_split_tn_group_kernel<4, 2, true>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         hipLaunchKernelGGL((gemm_split_tn_group_kernel<4, 2, true>), grid, dim3(256), lds, stream, g);
     } else if (mi == 4) {
@@ -1032,6 +1166,7 @@ int launch_quiet_tn_group(int n, const SplitTN* probs, hipStream_t stream) {
     int Mmax = 0, Nmax = 0, ztot = 0, tiles = 0;
     static const int target = arcvae_env_int("ARCVAE_SPLIT_BLOCKS", 256);
     for (int i = 0; i < n; ++i) {
+        if (probs[i].gap_len) return ARCVAE_ERR_ARG;           // (wgrad_quiet_kernel knows no gap)
         g.p[i] = probs[i];
         Mmax = max(Mmax, probs[i].M); Nmax = max(Nmax, probs[i].N);
         tiles += ceil_div(probs[i].M, 128) * ceil_div(probs[i].N, 128);
@@ -1194,16 +1329,21 @@ void launch_tile_t(const GemmP& p, dim3 grid, bool ak, bool bk, bool va4, bool v
 
 inline bool aligned16(const void* p) { return (reinterpret_cast<uintptr_t>(p) & 15) == 0; }
 
-}  // namespace
-
-extern "C" int arcvae_gemm_f32(int transA, int transB, int M, int N, int K,
-                               const float* A, int lda, const float* B, int ldb,
-                               float* C, int ldc, const float* bias, int flags, hipStream_t stream) {
+// arcvae_gemm_f32 with an optional gap (ops.h: arcvae_gemm_f32_gap).  *rode = the launch chosen took `colsum` as its rider.
+int gemm_f32_impl(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C, int ldc,
+                  const float* bias, int flags, int gap_dim, int gap_at, int gap_len, float* colsum, bool* rode,
+                  hipStream_t stream) {
     if (M <= 0 || N <= 0 || K <= 0 || !A || !B || !C) return ARCVAE_ERR_ARG;
-    if (lda < (transA ? M : K) || ldb < (transB ? K : N) || ldc < N) return ARCVAE_ERR_ARG;
+    if (gap_dim < 0 || gap_dim > 3 || (gap_dim && (gap_at <= 0 || gap_len <= 0 || (gap_at % 64) || (gap_len % 64)))) return ARCVAE_ERR_ARG;
+    if (!gap_dim) gap_at = gap_len = 0;
+    if (gap_dim && (flags & ARCVAE_GEMM_SPLITK) && !(flags & ARCVAE_GEMM_ACCUMULATE)) return ARCVAE_ERR_ARG;   // (the zero fill knows no gap)
+    const int Mp = M + (gap_dim == 1 ? gap_len : 0), Np = N + (gap_dim == 2 ? gap_len : 0), Kp = K + (gap_dim == 3 ? gap_len : 0);
+    if (lda < (transA ? Mp : Kp) || ldb < (transB ? Kp : Np) || ldc < Np) return ARCVAE_ERR_ARG;
+    const bool gap128 = (gap_dim == 1 || gap_dim == 2) && (gap_at % 128) != 0;   // a 128-wide block tile would straddle gap_at
     GemmP p;
     p.A = A; p.B = B; p.C = C; p.bias = bias;
     p.M = M; p.N = N; p.K = K; p.lda = lda; p.ldb = ldb; p.ldc = ldc;
+    p.gap_dim = gap_dim; p.gap_at = gap_at; p.gap_len = gap_len;
     p.accumulate = (flags & ARCVAE_GEMM_ACCUMULATE) ? 1 : 0;
     p.act = (flags & ARCVAE_GEMM_TANH) ? 1 : ((flags & ARCVAE_GEMM_DTANH) ? 2 : 0);
     if (p.act == 2 && (!bias || p.accumulate)) return ARCVAE_ERR_ARG;
@@ -1217,6 +1357,7 @@ extern "C" int arcvae_gemm_f32(int transA, int transB, int M, int N, int K,
     // ARCVAE_GEMM_QUIET: the LDS-staged form of the split-bf16 TN "+=" kernel, and nothing else (no other kernel is chosen
     // in its place: operands it cannot take are an argument error)
     if (flags & ARCVAE_GEMM_QUIET) {
+        if (gap_dim) return ARCVAE_ERR_ARG;
         if (!(transA && !transB && (flags & ARCVAE_GEMM_ACCUMULATE) && (flags & ARCVAE_GEMM_SPLITK)) || bias || p.act != 0 ||
             (flags & (ARCVAE_GEMM_TILE64 | ARCVAE_GEMM_TILE128 | ARCVAE_GEMM_TILE_WIDE | ARCVAE_GEMM_BF16 | ARCVAE_GEMM_SPLIT3)) ||
             !quiet_tn_ok(M, N, A, lda, B, ldb))
@@ -1228,9 +1369,12 @@ extern "C" int arcvae_gemm_f32(int transA, int transB, int M, int N, int K,
     // TN "+=" with split-K allowed (weight-gradient / token-table shapes): split-bf16 kernel
     if (!bf16_tile_tn)
     if (transA && !transB && (flags & ARCVAE_GEMM_ACCUMULATE) && (flags & ARCVAE_GEMM_SPLITK) && !bias && p.act == 0 &&
-        !(flags & (ARCVAE_GEMM_TILE64 | ARCVAE_GEMM_TILE128)) && split_tn_ok(M, N, A, lda, B, ldb)) {
+        !(flags & (ARCVAE_GEMM_TILE64 | ARCVAE_GEMM_TILE128)) && split_tn_ok(M, N, A, lda, B, ldb) && gap_dim != 2 && gap_dim != 3) {
         SplitTN q;
-        q.A = A; q.B = B; q.C = C; q.colsum = nullptr; q.M = M; q.N = N; q.K = K; q.lda = lda; q.ldb = ldb; q.ldc = ldc; q.kchunk = 0;
+        const bool ride = colsum != nullptr && arcvae_env_int("ARCVAE_COLSUM_FUSED", 1) != 0;   // 0: column sums by launch (A/B experiments)
+        if (ride) *rode = true;
+        q.gap_at = gap_at; q.gap_len = gap_len;
+        q.A = A; q.B = B; q.C = C; q.colsum = ride ? colsum : nullptr; q.M = M; q.N = N; q.K = K; q.lda = lda; q.ldb = ldb; q.ldc = ldc; q.kchunk = 0;
         return launch_split_tn_group(1, &q, (flags & ARCVAE_GEMM_TILE_WIDE) != 0, (flags & ARCVAE_GEMM_BF16) != 0, stream);
     }
     // ARCVAE_GEMM_SPLIT3: any layout on the bf16 matrix pipe at fp32-class accuracy -- three bf16 pieces per operand, six
@@ -1260,7 +1404,7 @@ extern "C" int arcvae_gemm_f32(int transA, int transB, int M, int N, int K,
         // 128 x 128 tiles when they fill the chip
         // (for the K-long weight-gradient shapes the 64 x 64 tile with 2 K slices measured 207 TFLOP/s, the 128 x 128 tile
         // with 20 slices 81: the float-atomic epilogue is paid per slice)
-        const bool big = M >= 128 && N >= 128 && ceil_div(M, 128) * ceil_div(N, 128) >= 256;
+        const bool big = M >= 128 && N >= 128 && ceil_div(M, 128) * ceil_div(N, 128) >= 256 && !gap128;
         const int bm = big ? 128 : 64;
         dim3 grid(ceil_div(N, bm), ceil_div(M, bm), 1);
         if ((flags & ARCVAE_GEMM_SPLITK) && p.act == 0) {
@@ -1279,7 +1423,8 @@ extern "C" int arcvae_gemm_f32(int transA, int transB, int M, int N, int K,
         p.kchunk = ((K + BK - 1) / BK) * BK;     // operands not vector-loadable: the f32 kernels below
     }
     // Skinny path: minibatch-sized M on the critical path.
-    if (!(flags & ARCVAE_GEMM_NO_SKINNY) && ak && M <= 256 && (K % 64) == 0 && (lda % 4) == 0 &&
+    // (a gap: in N either form; in K the [K, N] form, which keeps the wave partition of the physical K)
+    if (!(flags & ARCVAE_GEMM_NO_SKINNY) && ak && M <= 256 && (Kp % 64) == 0 && (lda % 4) == 0 && gap_dim != 1 && !(gap_dim == 3 && bk) &&
         aligned16(A) && (!bk || ((ldb % 4) == 0 && aligned16(B)))) {
         dim3 grid(ceil_div(N, 16), ceil_div(M, 16), 1);
         if (bk) hipLaunchKernelGGL(gemm_skinny_kernel<true>, grid, dim3(256), 0, stream, p);
@@ -1300,6 +1445,7 @@ extern "C" int arcvae_gemm_f32(int transA, int transB, int M, int N, int K,
     bool big = M >= 128 && N >= 128 && blocks128 >= 2048;
     if (flags & ARCVAE_GEMM_TILE128) big = true;
     if (flags & ARCVAE_GEMM_TILE64) big = false;
+    if (gap128) big = false;
     const int bm = big ? 128 : 64, bn = big ? 128 : 64;
     dim3 grid(ceil_div(N, bn), ceil_div(M, bm), 1);
     if ((flags & ARCVAE_GEMM_SPLITK) && p.act == 0) {
@@ -1320,6 +1466,31 @@ extern "C" int arcvae_gemm_f32(int transA, int transB, int M, int N, int K,
     if (big) launch_tile_t<128, 128>(p, grid, ak, bk, va4, vb4, stream);
     else launch_tile_t<64, 64>(p, grid, ak, bk, va4, vb4, stream);
     return arcvae_launch_status();
+}
+
+}  // namespace
+
+extern "C" int arcvae_gemm_f32(int transA, int transB, int M, int N, int K,
+                               const float* A, int lda, const float* B, int ldb,
+                               float* C, int ldc, const float* bias, int flags, hipStream_t stream) {
+    bool rode = false;
+    return gemm_f32_impl(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, 0, 0, 0, nullptr, &rode, stream);
+}
+
+// arcvae_gemm_f32 with a gap in one dimension (GemmP: gap_dim 1 M, 2 N, 3 K, 0 none; M, N, K are the logical extents) and, for the
+// TN form, colsum[m] += the column sums of A over K at the physical m (optional): as the split kernel's rider where that kernel
+// is the one chosen, by arcvae_colsum_accum launches over the columns outside the gap otherwise.  Internal (ops.h).
+int arcvae_gemm_f32_gap(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
+                        int ldc, const float* bias, int flags, int gap_dim, int gap_at, int gap_len, float* colsum,
+                        hipStream_t stream) {
+    if (colsum && !(transA && !transB)) return ARCVAE_ERR_ARG;
+    bool rode = false;
+    int rc = gemm_f32_impl(transA, transB, M, N, K, A, lda, B, ldb, C, ldc, bias, flags, gap_dim, gap_at, gap_len, colsum, &rode, stream);
+    if (rc || !colsum || rode) return rc;
+    if (gap_dim != 1) return arcvae_colsum_accum(A, K, M, lda, colsum, 1.0f, stream);
+    rc = arcvae_colsum_accum(A, K, gap_at, lda, colsum, 1.0f, stream);
+    if (rc || M <= gap_at) return rc;
+    return arcvae_colsum_accum(A + gap_at + gap_len, K, M - gap_at, lda, colsum + gap_at + gap_len, 1.0f, stream);
 }
 
 // Two skinny products in one launch (internal, ops.h): C_i[M_i,N_i] (+)= A_i[M_i,K_i] . op(B_i) (+ bias_i) (act_i), i = 0, 1;
@@ -1786,12 +1957,18 @@ int arcvae_wgrad_octet_group(int n, int M, int N, const int* K, const void* cons
 
 // h = zero_state_cell(A . W^T + bias) for a decoder layer whose pre-activations are not needed afterwards (gemm_cell_zero_kernel).
 // Internal (ops.h).  Returns ARCVAE_ERR_ARG when the operands do not allow the 16-byte loads (the caller then takes the two-launch path).
+// three_gates: gemm_cell_zero3_kernel (the forget gate's columns are not computed); 0: all four (gemm_cell_zero_kernel).
 int arcvae_gemm_cell_zero(int M, int H, int K, const float* A, int lda, const float* W, int ldw, const float* bias,
-                          float* Hout, hipStream_t stream) {
+                          float* Hout, int three_gates, hipStream_t stream) {
     if (M <= 0 || H <= 0 || K <= 0 || !A || !W || !bias || !Hout) return ARCVAE_ERR_ARG;
     if ((K % 4) != 0 || (lda % 4) != 0 || (ldw % 4) != 0 || !aligned16(A) || !aligned16(W) || lda < K || ldw < K) return ARCVAE_ERR_ARG;
     CellGemmP p;
     p.A = A; p.W = W; p.bias = bias; p.Hout = Hout; p.M = M; p.H = H; p.K = K; p.lda = lda; p.ldw = ldw;
+    if (three_gates) {
+        const int lds3 = (int)sizeof(float) * 64 * 193;   // >= the operand tiles' 2 * 16 * (68 + 196) floats
+        hipLaunchKernelGGL(gemm_cell_zero3_kernel, dim3(ceil_div(H, 64), ceil_div(M, 64)), dim3(256), lds3, stream, p);
+        return arcvae_launch_status();
+    }
     const int lds = (int)sizeof(float) * 128 * 129;   // >= the operand tiles' 2 * 16 * (132 + 132) floats
     (void)hipFuncSetAttribute((const void*)gemm_cell_zero_kernel, hipFuncAttributeMaxDynamicSharedMemorySize, lds);
     hipLaunchKernelGGL(gemm_cell_zero_kernel, dim3(ceil_div(4 * H, 128), ceil_div(M, 128)), dim3(256), lds, stream, p);

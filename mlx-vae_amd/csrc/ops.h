@@ -11,6 +11,13 @@ int arcvae_gemm_tn_group_accum(int n, int M, int N, const int* K, const float* c
                                const float* const* B, int ldb, float* const* C, int ldc, int allow_split,
                                float* const* colsum /* optional: colsum_i[M] += column sums of A_i */, hipStream_t stream);
 
+// internal (C++ linkage): arcvae_gemm_f32 with a gap in one dimension, see gemm.hip.  gap_dim: 0 none, 1 M, 2 N, 3 K; M, N, K are the
+// LOGICAL extents; tiles at or beyond gap_at (a multiple of 64, as is gap_len) address gap_len further on in the operands, the bias
+// and C.  colsum (optional, TN form only): colsum[m] += column sums of A over K -- the split kernel's rider where that kernel runs.
+int arcvae_gemm_f32_gap(int transA, int transB, int M, int N, int K, const float* A, int lda, const float* B, int ldb, float* C,
+                        int ldc, const float* bias, int flags, int gap_dim, int gap_at, int gap_len, float* colsum,
+                        hipStream_t stream);
+
 // internal (C++ linkage): throughput mode, weight gradients from octet-major bf16 operand copies, see gemm.hip
 int arcvae_wgrad_octet_group(int n, int M, int N, const int* K, const void* const* A, const void* const* B,
                              float* const* C, int ldc, hipStream_t stream);
@@ -21,8 +28,9 @@ int arcvae_wgrad_planes_group(int n, int M, int N, int rows, const void* const* 
                               hipStream_t stream);
 
 // internal (C++ linkage): a forward-only decoder layer (GEMM + zero-state cell, no pre-activations kept), see gemm.hip
+// three_gates: the forget gate's columns are not computed (the zero-state cell never reads them)
 int arcvae_gemm_cell_zero(int M, int H, int K, const float* A, int lda, const float* W, int ldw, const float* bias,
-                          float* Hout, hipStream_t stream);
+                          float* Hout, int three_gates, hipStream_t stream);
 
 // internal (C++ linkage): two skinny products in one launch, see gemm.hip
 int arcvae_gemm_skinny_pair(int transB, const int* M, const int* N, const int* K, const float* const* A, const int* lda,

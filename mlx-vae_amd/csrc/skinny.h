@@ -58,7 +58,7 @@ __device__ __forceinline__ void skinny_accum_kk(f32x4& acc0, f32x4& acc1,
 __device__ __forceinline__ void skinny_accum_kn(f32x4& acc0, f32x4& acc1,
                                                 const float* __restrict__ A, long arow_off,
                                                 const float* __restrict__ W, int ldw, int wcol,
-                                                int K, int wave, int lane) {
+                                                int K, int wave, int lane, int skip_lo = 0, int skip_hi = 0) {
     const int Kw = K >> 2;
     const int kbase = wave * Kw + (lane >> 4) * 4;
     const float4* ap = reinterpret_cast<const float4*>(A + arow_off + kbase);
@@ -66,6 +66,8 @@ __device__ __forceinline__ void skinny_accum_kn(f32x4& acc0, f32x4& acc1,
     const int nchunk = Kw >> 4;
 #pragma unroll 4
     for (int c = 0; c < nchunk; ++c) {
+        const int kc = wave * Kw + 16 * c;             // chunks inside [skip_lo, skip_hi) (multiples of 16) are passed over
+        if (kc >= skip_lo && kc < skip_hi) continue;
         const float4 a0 = ap[4 * c];
         float4 b0;
         b0.x = wp[(long)(16 * c + 0) * ldw];
