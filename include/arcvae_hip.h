@@ -373,6 +373,41 @@ int arcvae_dec_beam_search(const float* dense_logits, const float* lse, int32_t*
                            float temperature, arcvae_stream_t stream);
 int arcvae_dec_sequence_logprob(const float* dense_logits, const float* lse, const int32_t* tokens, float* out, int B, int T, int V,
                                 int end_token, float temperature, arcvae_stream_t stream);
+/* EXTENSION (no reference counterpart: the reference decodes greedily) -- exact MAP decoding and exact chain marginals over the
+ * dense logits [B*V, V] of arcvae_dec_forward_dense (mode 0).  Given its conditions a batch row's generator is a first-order Markov
+ * chain over the V tokens (the decoder is stateless per step), and rows b*V .. b*V+V-1 of the table are its transition matrix.
+ * Step term and score are the beam contract's: lp(c, v) = fl(fl(x[b*V+c, v] * fl(1.0f / temperature)) - lse[b*V+c]) with lse from
+ * arcvae_dec_row_lse, a prefix score fl(s + lp), one IEEE fp32 operation at a time, no contraction; the start token is 0.
+ * Limits of both: 1 <= V <= 256, 0 <= end_token < V, max_len >= 1, temperature finite and > 0; arcvae_dec_viterbi also
+ * 0 <= min_len <= max_len, 0 <= pad_token <= 255, ws_bytes >= arcvae_dec_viterbi_ws_bytes(B, V, max_len) (the back pointers, bytes
+ * [B, max_len, V], caller-owned device scratch).  Anything else (a null pointer, a NaN temperature) is ARCVAE_ERR_ARG before any
+ * launch.  Neither allocates nor keeps host state; both are asynchronous on `stream` and capture-safe.
+ * arcvae_dec_viterbi, per batch row.  Admissible sequences x_0 .. x_{n-1}: either x_{n-1} = end_token with no earlier end_token and
+ *   n-1 >= min_len, or n = max_len with no end_token at all.  Score: the left-to-right fp32 sum s <- fl(s + lp(fed_t, x_t)) from
+ *   s = 0, fed_0 = 0, fed_t = x_{t-1} (what arcvae_dec_sequence_logprob returns for the tokens).  Recursion, for v != end_token:
+ *   a_0[v] = fl(0 + lp(0, v)), a_t[v] = max over u != end_token of fl(a_{t-1}[u] + lp(u, v)), back pointer = the LOWEST u that
+ *   attains the maximum; the end candidate e_t of a step t >= min_len is the same maximum into v = end_token (e_0 = fl(0 +
+ *   lp(0, end_token))).  Result: the candidates e_{min_len}, ..., e_{max_len-1}, then a_{max_len-1}[v] for v != end_token in
+ *   ascending v, scanned in that order; the first one is taken and a later one replaces it only when strictly greater -- on ties
+ *   the earliest-ending sequence wins, then the lowest last token.  tokens [B, max_len] = the sequence, pad_token after its end;
+ *   length [B] = n; score [B] = its score.
+ *   Exactness: x -> fl(x + c) is monotone (non-decreasing) in x for IEEE round-to-nearest, so the best fp32 score of a prefix
+ *   ending in v extends to the best fp32 score of every continuation: a_t[v] IS the maximum of the contract score over all
+ *   end-free prefixes x_0 .. x_t = v, and the result IS the maximum over all admissible sequences -- exactly, not approximately,
+ *   and never below any beam width's best hypothesis under the same min_len.  (Monotone, not strictly: two prefixes may round to
+ *   one score; the tie rules above then say which sequence is returned.)
+ *   A row holding a NaN or an infinite logit is outside the contract; it still writes tokens in [0, V) (and pad_token).  V = 1
+ *   with min_len = max_len admits no sequence: score -inf, length max_len, tokens 0.
+ * arcvae_dec_chain_marginals: with p(c, v) = expf(lp(c, v)), alive[b, 0, v] = p(0, v) and alive[b, t, v] = sum over u != end_token
+ *   of alive[b, t-1, u] * p(u, v) = P(token at step t is v and no end_token before t), alive [B, max_len, V].  fp32 sums in the
+ *   kernel's own, fixed order; no atomics: repeated calls are bitwise identical.  alive[b, t, end_token] = P(length = t+1) of what
+ *   arcvae_dec_sample_chain_categorical draws; sum over v != end_token of alive[b, max_len-1, v] = P(no end within max_len). */
+int arcvae_dec_viterbi_ws_bytes(int B, int V, int max_len, long* bytes);
+int arcvae_dec_viterbi(const float* dense_logits, const float* lse, int32_t* tokens, float* score, int32_t* length, void* ws,
+                       long ws_bytes, int B, int V, int max_len, int min_len, int end_token, int pad_token, float temperature,
+                       arcvae_stream_t stream);
+int arcvae_dec_chain_marginals(const float* dense_logits, const float* lse, float* alive, int B, int V, int max_len, int end_token,
+                               float temperature, arcvae_stream_t stream);
 /* EXTENSION (no reference counterpart: the reference decodes greedily) -- top-k / nucleus (top-p) truncated sampling over the dense
  * logits [B*V, V] of arcvae_dec_forward_dense (mode 0); row r = b*V + c holds batch row b's logits after token c.
  * 1 <= vocab_size <= 256, temperature > 0, top_k >= 0 (0 = all V), 0 < top_p <= 1; anything else (NaN included) is ARCVAE_ERR_ARG.

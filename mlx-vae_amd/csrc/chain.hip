@@ -1,0 +1,319 @@
+// Exact MAP decoding (Viterbi) and exact chain marginals (forward recursion) over the dense decoder table -- an EXTENSION with no
+// reference behaviour to match (the reference's sampler is the greedy walk, models/decoder_sampling.py:48-128).
+//
+// The decoder is stateless per step: given its conditions, a batch row's generator is a first-order Markov chain
+// over at most 256 tokens, and rows b*V .. b*V+V-1 of the dense table (arcvae_dec_forward_dense, mode 0) are its transition
+// matrix.  The step term is the beam contract's (beam.hip), in fp32 with no contraction:
+//     lp(c, v) = fl(fl(x[b*V+c, v] * inv_temp) - lse_T[b*V+c]),      a prefix score = fl(s + lp).
+// The contract of both entry points is stated once, in include/arcvae_hip.h; tests/chain_ref.py restates it in NumPy.
+//
+// Kernels: one 256-thread workgroup per batch row.  The u range of a step's V x V products is cut into P contiguous parts of S
+// tokens (S a multiple of 4); thread (p, v) scans part p of column v, in ascending u, against the previous step's vector in LDS
+// (read four u at a time), and the threads of part 0 merge the P partial results in ascending p.  For the maximum that keeps
+// "the lowest u wins a tie" (a strict > in both passes); for the sum it fixes the summation order.  Two barriers per step
+// (one when P = 1); the vector is double-buffered.  The row's V x V step terms (Viterbi) or probabilities (marginals) are
+// computed once into LDS when V <= CHAIN_STAGE_V and read from the table through L2 otherwise.  The end token never continues:
+// its entry of the vector is -inf (maximum) or 0 (sum), as are the entries that pad V to a multiple of 4, so neither needs a
+// branch in the scan.
+//   viterbi    back pointers go to the caller's scratch as bytes [B, max_len, V]; the back-trace stages them through LDS in
+//              chunks of CHAIN_TRACE_BYTES and one thread follows them.
+//   marginals  writes alive[b, t, :] every step.
+#include "common.h"
+
+namespace {
+
+constexpr int CHAIN_MAX_V = 256;
+constexpr int CHAIN_THREADS = 256;
+constexpr int CHAIN_STAGE_V = 96;           // largest V whose V x V table is staged (36 KB: three workgroups per CU; V 80: five)
+constexpr int CHAIN_TRACE_BYTES = 8192;     // back pointers staged per chunk of the back-trace (>= 32 steps at V 256)
+// LDS (floats): vector A [256] | vector B [256] | partial results [256] x 2 (Viterbi: value and argument; the sum uses 256) |
+// lse [256] | control [4] (int / float) | table, or the back-trace's chunk
+constexpr int CHAIN_OFF_B = 256, CHAIN_OFF_PV = 512, CHAIN_OFF_LSE = 1024, CHAIN_OFF_CTL = 1280,
+              CHAIN_OFF_TAB = 1284;
+
+struct ChainPlan {
+    int S, P;          // tokens per part, parts: (P - 1) * S < V <= P * S, P * V <= CHAIN_THREADS
+    bool staged;
+    unsigned lds;      // dynamic LDS bytes
+};
+
+ChainPlan chain_plan(int V, bool trace) {
+    ChainPlan p;
+    int S = ceil_div(V, CHAIN_THREADS / V);
+    S = (S + 3) & ~3;
+    if (S < 8) S = 8;                      // shorter parts cost more in the merge than they save in the scan
+    p.S = S;
+    p.P = ceil_div(V, S);
+    p.staged = V <= CHAIN_STAGE_V;
+    const int V4 = (V + 3) & ~3;
+    unsigned tail = p.staged ? (unsigned)(V4 * V * 4) : 0u;
+    if (trace && tail < (unsigned)CHAIN_TRACE_BYTES) tail = CHAIN_TRACE_BYTES;
+    p.lds = CHAIN_OFF_TAB * 4 + tail;
+    return p;
+}
+
+// The row's lse into LDS, and (STAGED) its table: lp, or expf(lp) for the sum; rows V .. V4-1 are zero.
+template <bool STAGED, bool EXP>
+__device__ __forceinline__ void chain_stage(const float* __restrict__ x, const float* __restrict__ lse, float* ls, float* tab, int V,
+                                            float inv_temp) {
+    const int tid = threadIdx.x;
+    if (tid < V) ls[tid] = lse[tid];
+    __syncthreads();
+    if (STAGED) {
+        const int V4 = (V + 3) & ~3;
+        for (int i = tid; i < V4 * V; i += CHAIN_THREADS) {
+            float lp = 0.f;
+            if (i < V * V) {
+                const float a = x[i] * inv_temp;
+                lp = a - ls[i / V];
+                if (EXP) lp = expf(lp);
+            }
+            tab[i] = lp;
+        }
+        __syncthreads();
+    }
+}
+
+// Step term of (u, v); u in [V, V4) reads a row that exists (its vector entry is -inf or 0).
+template <bool STAGED, bool EXP>
+__device__ __forceinline__ float chain_term(const float* tab, const float* __restrict__ x, const float* ls, int u, int v, int V,
+                                            float inv_temp) {
+    if (STAGED) return tab[u * V + v];
+    const int r = min(u, V - 1);
+    const float a = x[(long)r * V + v] * inv_temp;
+    const float lp = a - ls[r];
+    return EXP ? expf(lp) : lp;
+}
+
+// Four consecutive entries of the previous step's vector (u a multiple of 4) and their step terms into column v.
+struct ChainQuad {
+    float4 a;
+    float t0, t1, t2, t3;
+};
+template <bool STAGED, bool EXP>
+__device__ __forceinline__ ChainQuad chain_quad(const float* cur, const float* tab, const float* __restrict__ x, const float* ls,
+                                                int u, int v, int V, float inv_temp) {
+    ChainQuad q;
+    q.a = *(const float4*)(cur + u);
+    q.t0 = chain_term<STAGED, EXP>(tab, x, ls, u, v, V, inv_temp);
+    q.t1 = chain_term<STAGED, EXP>(tab, x, ls, u + 1, v, V, inv_temp);
+    q.t2 = chain_term<STAGED, EXP>(tab, x, ls, u + 2, v, V, inv_temp);
+    q.t3 = chain_term<STAGED, EXP>(tab, x, ls, u + 3, v, V, inv_temp);
+    return q;
+}
+
+// ---- Viterbi -----------------------------------------------------------------------------------------------------------------
+template <bool STAGED>
+__global__ __launch_bounds__(CHAIN_THREADS) void chain_viterbi_kernel(const float* __restrict__ logits,
+                                                                      const float* __restrict__ lse, uint8_t* bp, int32_t* tokens,
+                                                                      float* score, int32_t* length, int V, int S, int P,
+                                                                      int max_len, int min_len, int end_token, int pad_token,
+                                                                      float inv_temp) {
+    extern __shared__ __align__(16) float smem[];
+    float* cur = smem;
+    float* nxt = smem + CHAIN_OFF_B;
+    unsigned long long* pp = (unsigned long long*)(smem + CHAIN_OFF_PV);   // a part's maximum (low word) and argument, per column
+    float* ls = smem + CHAIN_OFF_LSE;
+    int* ctl = (int*)(smem + CHAIN_OFF_CTL);
+    float* tab = smem + CHAIN_OFF_TAB;
+    uint8_t* stage = (uint8_t*)tab;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int p = tid / V, v = tid - p * V;
+    const bool active = p < P, owner = p == 0;               // owner: thread v of part 0 holds column v's merged result
+    const int V4 = (V + 3) & ~3;
+    const int lo = p * S, hi = min(lo + S, V4);
+    const float* x = logits + (long)b * V * V;
+    uint8_t* bpb = bp + (long)b * max_len * V;
+    int32_t* out = tokens + (long)b * max_len;
+
+    chain_stage<STAGED, false>(x, lse + (long)b * V, ls, tab, V, inv_temp);
+    cur[tid] = -INFINITY;                                     // (the pads V .. V4-1 stay -inf in both vectors)
+    nxt[tid] = -INFINITY;
+    __syncthreads();
+    // the best end candidate so far, kept by the end token's owner: e_t of the earliest t that attains the maximum
+    float res = 0.f;
+    int res_t = 0;
+    bool have = false;
+    if (owner) {
+        const float s = 0.f + chain_term<STAGED, false>(tab, x, ls, 0, v, V, inv_temp);
+        if (v == end_token) {
+            if (min_len == 0) { res = s; have = true; }
+        } else {
+            cur[v] = s;
+        }
+    }
+    __syncthreads();
+    for (int t = 1; t < max_len; ++t) {
+        float best = -INFINITY;
+        int arg = min(lo, V - 1);
+        if (active) {
+            for (int u = lo; u < hi; u += 4) {
+                const ChainQuad c = chain_quad<STAGED, false>(cur, tab, x, ls, u, v, V, inv_temp);
+                const float s0 = c.a.x + c.t0, s1 = c.a.y + c.t1, s2 = c.a.z + c.t2, s3 = c.a.w + c.t3;
+                if (s0 > best) { best = s0; arg = u; }
+                if (s1 > best) { best = s1; arg = u + 1; }
+                if (s2 > best) { best = s2; arg = u + 2; }
+                if (s3 > best) { best = s3; arg = u + 3; }
+            }
+            if (!owner) pp[tid] = (unsigned long long)__float_as_uint(best) | ((unsigned long long)(unsigned)arg << 32);
+        }
+        if (P > 1) __syncthreads();
+        if (owner) {
+            for (int q = 1; q < P; ++q) {
+                const unsigned long long e = pp[q * V + v];    // (one 8-byte read: value and argument arrive together)
+                const float s = __uint_as_float((unsigned)e);
+                if (s > best) { best = s; arg = (int)(e >> 32); }
+            }
+            bpb[(long)t * V + v] = (uint8_t)arg;
+            if (v == end_token) {
+                if (t >= min_len && (!have || best > res)) { res = best; res_t = t; have = true; }
+            } else {
+                nxt[v] = best;
+            }
+        }
+        __syncthreads();
+        float* sw = cur;
+        cur = nxt;
+        nxt = sw;
+    }
+    // the result: the end candidates (above), then a_{max_len-1}[v], v != end_token ascending; a later one wins only when
+    // strictly greater.  The first candidate is taken whatever it holds, so a row outside the contract still yields tokens.
+    if (owner && v == end_token) {
+        ctl[0] = have;
+        ctl[1] = res_t;
+        ((float*)ctl)[2] = res;
+    }
+    __syncthreads();
+    if (tid == 0) {
+        bool chosen = ctl[0] != 0;
+        float bs = chosen ? ((float*)ctl)[2] : -INFINITY;
+        int n = chosen ? ctl[1] + 1 : max_len, last = chosen ? end_token : 0;
+        for (int w = 0; w < V; ++w) {
+            if (w == end_token) continue;
+            const float s = cur[w];
+            if (!chosen || s > bs) { bs = s; n = max_len; last = w; chosen = true; }
+        }
+        score[b] = bs;
+        length[b] = n;
+        out[n - 1] = last;
+        ctl[1] = n;
+        ctl[3] = last;
+    }
+    __syncthreads();
+    const int n = ctl[1];
+    for (int t = n + tid; t < max_len; t += CHAIN_THREADS) out[t] = pad_token;
+    // back-trace: x_{t-1} = bp[t][x_t] for t = n-1 .. 1, the rows [c0, top) of a chunk staged in LDS (the table is dead)
+    const int rows = CHAIN_TRACE_BYTES / V;
+    int tok = ctl[3];
+    for (int top = n; top > 1; top -= rows) {
+        const int c0 = max(1, top - rows), nb = (top - c0) * V;
+        for (int i = tid; i < nb; i += CHAIN_THREADS) stage[i] = bpb[(long)c0 * V + i];
+        __syncthreads();
+        if (tid == 0) {
+            for (int t = top - 1; t >= c0; --t) {
+                tok = min((int)stage[(t - c0) * V + tok], V - 1);
+                out[t - 1] = tok;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// ---- forward recursion -------------------------------------------------------------------------------------------------------
+template <bool STAGED>
+__global__ __launch_bounds__(CHAIN_THREADS) void chain_marginals_kernel(const float* __restrict__ logits,
+                                                                        const float* __restrict__ lse, float* alive, int V, int S,
+                                                                        int P, int max_len, int end_token, float inv_temp) {
+    extern __shared__ __align__(16) float smem[];
+    float* cur = smem;
+    float* nxt = smem + CHAIN_OFF_B;
+    float* pv = smem + CHAIN_OFF_PV;
+    float* ls = smem + CHAIN_OFF_LSE;
+    float* tab = smem + CHAIN_OFF_TAB;
+    const int tid = threadIdx.x, b = blockIdx.x;
+    const int p = tid / V, v = tid - p * V;
+    const bool active = p < P, owner = p == 0;
+    const int V4 = (V + 3) & ~3;
+    const int lo = p * S, hi = min(lo + S, V4);
+    const float* x = logits + (long)b * V * V;
+    float* ob = alive + (long)b * max_len * V;
+
+    chain_stage<STAGED, true>(x, lse + (long)b * V, ls, tab, V, inv_temp);
+    cur[tid] = 0.f;                                           // (the pads V .. V4-1 and the end token stay 0 in both vectors)
+    nxt[tid] = 0.f;
+    __syncthreads();
+    if (owner) {
+        const float s = chain_term<STAGED, true>(tab, x, ls, 0, v, V, inv_temp);
+        ob[v] = s;
+        if (v != end_token) cur[v] = s;
+    }
+    __syncthreads();
+    for (int t = 1; t < max_len; ++t) {
+        float acc = 0.f;
+        if (active) {
+            for (int u = lo; u < hi; u += 4) {
+                const ChainQuad c = chain_quad<STAGED, true>(cur, tab, x, ls, u, v, V, inv_temp);
+                acc = fmaf(c.a.x, c.t0, acc);
+                acc = fmaf(c.a.y, c.t1, acc);
+                acc = fmaf(c.a.z, c.t2, acc);
+                acc = fmaf(c.a.w, c.t3, acc);
+            }
+            if (!owner) pv[tid] = acc;
+        }
+        if (P > 1) __syncthreads();
+        if (owner) {
+            for (int q = 1; q < P; ++q) acc += pv[q * V + v];
+            ob[(long)t * V + v] = acc;
+            if (v != end_token) nxt[v] = acc;
+        }
+        __syncthreads();
+        float* sw = cur;
+        cur = nxt;
+        nxt = sw;
+    }
+}
+
+bool chain_args_ok(const void* logits, const void* lse, int B, int V, int max_len, int end_token, float temperature) {
+    if (!logits || !lse || B <= 0 || V < 1 || V > CHAIN_MAX_V || max_len < 1 || end_token < 0 || end_token >= V) return false;
+    return temperature > 0.f && temperature <= 3.402823466e+38f;          // finite and > 0 (a NaN compares false)
+}
+
+}  // namespace
+
+extern "C" int arcvae_dec_viterbi_ws_bytes(int B, int V, int max_len, long* bytes) {
+    if (!bytes || B <= 0 || V < 1 || V > CHAIN_MAX_V || max_len < 1) return ARCVAE_ERR_ARG;
+    *bytes = (long)B * max_len * V;
+    return ARCVAE_OK;
+}
+
+extern "C" int arcvae_dec_viterbi(const float* dense_logits, const float* lse, int32_t* tokens, float* score, int32_t* length,
+                                  void* ws, long ws_bytes, int B, int V, int max_len, int min_len, int end_token, int pad_token,
+                                  float temperature, hipStream_t stream) {
+    if (!chain_args_ok(dense_logits, lse, B, V, max_len, end_token, temperature)) return ARCVAE_ERR_ARG;
+    if (!tokens || !score || !length || !ws || min_len < 0 || min_len > max_len || pad_token < 0 || pad_token > 255)
+        return ARCVAE_ERR_ARG;
+    if (ws_bytes < (long)B * max_len * V) return ARCVAE_ERR_ARG;
+    const ChainPlan pl = chain_plan(V, true);
+    const float inv_temp = 1.0f / temperature;
+    if (pl.staged)
+        hipLaunchKernelGGL(chain_viterbi_kernel<true>, dim3(B), dim3(CHAIN_THREADS), pl.lds, stream, dense_logits, lse, (uint8_t*)ws,
+                           tokens, score, length, V, pl.S, pl.P, max_len, min_len, end_token, pad_token, inv_temp);
+    else
+        hipLaunchKernelGGL(chain_viterbi_kernel<false>, dim3(B), dim3(CHAIN_THREADS), pl.lds, stream, dense_logits, lse,
+                           (uint8_t*)ws, tokens, score, length, V, pl.S, pl.P, max_len, min_len, end_token, pad_token, inv_temp);
+    return arcvae_launch_status();
+}
+
+extern "C" int arcvae_dec_chain_marginals(const float* dense_logits, const float* lse, float* alive, int B, int V, int max_len,
+                                          int end_token, float temperature, hipStream_t stream) {
+    if (!chain_args_ok(dense_logits, lse, B, V, max_len, end_token, temperature) || !alive) return ARCVAE_ERR_ARG;
+    const ChainPlan pl = chain_plan(V, false);
+    const float inv_temp = 1.0f / temperature;
+    if (pl.staged)
+        hipLaunchKernelGGL(chain_marginals_kernel<true>, dim3(B), dim3(CHAIN_THREADS), pl.lds, stream, dense_logits, lse, alive, V,
+                           pl.S, pl.P, max_len, end_token, inv_temp);
+    else
+        hipLaunchKernelGGL(chain_marginals_kernel<false>, dim3(B), dim3(CHAIN_THREADS), pl.lds, stream, dense_logits, lse, alive, V,
+                           pl.S, pl.P, max_len, end_token, inv_temp);
+    return arcvae_launch_status();
+}

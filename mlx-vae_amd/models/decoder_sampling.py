@@ -7,7 +7,9 @@ early stopping the output is cut where every row has emitted EOS.  One dense dec
 host sync; `load_from_decoder` is an explicit extension to sample from trained weights, and `sample=True` the true categorical
 sampling the reference marks TODO (decoder_sampling.py:115-116): an extension with no reference behaviour to match.  So is
 `generate_beam` (beam search with scores, csrc/beam.hip); `decoder.sequence_log_prob` scores given sequences; and
-`sample=True` with `top_k` / `top_p` (truncated sampling, csrc/sample.hip)."""
+`sample=True` with `top_k` / `top_p` (truncated sampling, csrc/sample.hip); and `generate_map` / `token_marginals` /
+`length_distribution`: the exact most probable sequence and the exact per-step token and length distributions of the chain the
+dense table defines (csrc/chain.hip)."""
 from __future__ import annotations
 
 import torch
@@ -207,3 +209,70 @@ class MLXAutoregressiveDecoderSampling:
         if early_stopping:
             tokens = tokens[:, :, :int(lengths.max().item())].contiguous()
         return tokens, scores
+
+    def _chain_table(self, conditions, max_length: int, temperature: float):
+        """The dense pass (mode 0) and the rows' lse for `conditions` -> (logits [B*V, V] in the workspace, lse [B*V], B)."""
+        dec = self.decoder
+        if not 0.0 < float(temperature) < float("inf"):
+            raise ValueError("temperature must be finite and > 0")
+        if int(max_length) < 1:
+            raise ValueError("need max_length >= 1")
+        if dec.vocab_size > 256 or not 0 <= self.end_token < dec.vocab_size:
+            raise ValueError("needs vocab_size <= 256 and 0 <= end_token < vocab_size")
+        dev = dec.store.device
+        cond = as_f32(conditions, dev)
+        B = cond.shape[0]
+        ws = dec.workspace(B, int(max_length))
+        ws.cond.copy_(cond.reshape(B, dec.num_conditions))
+        lse = torch.empty(B * dec.vocab_size, dtype=torch.float32, device=dev)
+        E.decoder_forward_dense(dec.store, ws, dec.dims, mode=0, keep_gpre=False, alone=True)
+        call("arcvae_dec_row_lse", ptr(ws.logits), ptr(lse), B * dec.vocab_size, dec.vocab_size, float(temperature), stream_ptr())
+        return ws.logits, lse, B
+
+    def generate_map(self, z, conditions, max_length: int = 80, temperature: float = 1.0, min_length: int = 0,
+                     early_stopping: bool = True):
+        """Extension (absent in the reference): the MOST PROBABLE sequence per row under log_softmax(logits / T), exactly -- a
+        Viterbi recursion over the dense table (include/arcvae_hip.h arcvae_dec_viterbi) -> (tokens [B, L] int32, scores [B]
+        float32).  z is accepted and unused (Q2).  A sequence ends with its first end_token, not before step min_length, or runs
+        to max_length without one; positions after the end hold pad_token; ties go to the earliest end, then the lowest tokens.
+        early_stopping: L = the longest returned sequence; otherwise L = max_length.  Each score equals
+        decoder.sequence_log_prob of its tokens bit for bit, and is never below generate_beam's best at any width."""
+        import ctypes as C
+        T = int(max_length)
+        if T < 1 or not 0 <= int(min_length) <= T:
+            raise ValueError("need max_length >= 1 and 0 <= min_length <= max_length")
+        if not 0 <= self.pad_token <= 255:
+            raise ValueError("exact decoding needs 0 <= pad_token <= 255")
+        logits, lse, B = self._chain_table(conditions, T, temperature)
+        V, dev = self.decoder.vocab_size, self.decoder.store.device
+        nbytes = C.c_long(0)
+        call("arcvae_dec_viterbi_ws_bytes", B, V, T, C.byref(nbytes))
+        scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        tokens = torch.empty(B, T, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, dtype=torch.float32, device=dev)
+        lengths = torch.empty(B, dtype=torch.int32, device=dev)
+        call("arcvae_dec_viterbi", ptr(logits), ptr(lse), ptr(tokens), ptr(scores), ptr(lengths), ptr(scratch), nbytes.value, B, V,
+             T, int(min_length), self.end_token, self.pad_token, float(temperature), stream_ptr())
+        if early_stopping:
+            tokens = tokens[:, :int(lengths.max().item())].contiguous()
+        return tokens, scores
+
+    def token_marginals(self, conditions, max_length: int = 80, temperature: float = 1.0) -> torch.Tensor:
+        """Extension (absent in the reference): [B, max_length, V] float32, entry [b, t, v] = P(the token at step t is v and no
+        end_token came before t) of what sample=True draws at this temperature -- the chain's forward recursion, exact up to fp32
+        rounding (include/arcvae_hip.h arcvae_dec_chain_marginals).  Column end_token is the length distribution."""
+        T = int(max_length)
+        logits, lse, B = self._chain_table(conditions, T, temperature)
+        V = self.decoder.vocab_size
+        alive = torch.empty(B, T, V, dtype=torch.float32, device=self.decoder.store.device)
+        call("arcvae_dec_chain_marginals", ptr(logits), ptr(lse), ptr(alive), B, V, T, self.end_token, float(temperature),
+             stream_ptr())
+        return alive
+
+    def length_distribution(self, conditions, max_length: int = 80, temperature: float = 1.0) -> torch.Tensor:
+        """[B, max_length + 1] float32: entry t < max_length = P(length = t+1) (the end_token column of token_marginals), the
+        last entry = P(no end_token within max_length), the mass a max_length cuts off."""
+        alive = self.token_marginals(conditions, max_length, temperature)
+        last = alive[:, -1, :]
+        rest = last.sum(dim=1) - last[:, self.end_token]
+        return torch.cat([alive[:, :, self.end_token], rest[:, None]], dim=1)
