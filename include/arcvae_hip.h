@@ -408,6 +408,38 @@ int arcvae_dec_viterbi(const float* dense_logits, const float* lse, int32_t* tok
                        arcvae_stream_t stream);
 int arcvae_dec_chain_marginals(const float* dense_logits, const float* lse, float* alive, int B, int V, int max_len, int end_token,
                                float temperature, arcvae_stream_t stream);
+/* EXTENSION (no reference counterpart) -- exact K-best decoding: the K most probable admissible sequences per batch row of the same
+ * first-order chain, by a list-Viterbi recursion.  The step term lp, the score, the start token 0, the admissible sequences and the
+ * limits are exactly those of arcvae_dec_viterbi, plus 1 <= K <= 32 and ws_bytes >= arcvae_dec_kbest_ws_bytes(B, V, K, max_len);
+ * anything else is ARCVAE_ERR_ARG before any launch.  Keeps no host state; asynchronous on `stream`; capture-safe.  All arithmetic
+ * is one IEEE fp32 addition per candidate, fl(s + lp), no contraction.
+ * Lists: a_t[v] is a list of at most K scores, non-increasing; rank r has the back pointer (u, r').  a_0[v] = [fl(0 + lp(0, v))].
+ *   For t >= 1 the candidates into column v are fl(a_{t-1}[u][r'] + lp(u, v)) for every u != end_token and every non-empty rank r',
+ *   enumerated in (u ascending, r' ascending) order; a_t[v] is the first K of a STABLE sort of them by score descending, i.e. the
+ *   order is (score desc, u asc, r' asc).  An empty entry is -inf and is never a candidate.  After step t column end_token is
+ *   emptied: the end token never continues.
+ * Result: the result candidates arrive in this order: for t = min_len .. max_len-1 the list into end_token at step t, by rank
+ *   ascending; then, for v != end_token ascending, the list a_{max_len-1}[v], by rank ascending.  The result is the first K of a
+ *   stable sort of that sequence by score descending: on ties the earlier-ending sequence comes first, then the lower last token,
+ *   then the lower rank.
+ * Outputs: scores [B, K] descending; tokens [B, K, max_len] = the sequence followed back through the (u, r') pointers, pad_token
+ *   after its end; lengths [B, K] = n.  A slot with no candidate (fewer than K admissible sequences) holds score -inf, length 0
+ *   and pad tokens only, like an empty beam slot.
+ * Exactness: x -> fl(x + c) is monotone, so a prefix dropped at (t, v) has K kept prefixes whose every common continuation scores
+ *   at least as high.  Hence scores[b, :] IS the multiset of the K largest contract scores over all admissible sequences; the K
+ *   sequences are pairwise distinct; each score is what arcvae_dec_sequence_logprob returns for its tokens; rank j is never below
+ *   rank j of any K-wide beam under the same min_len; and with K = 1 the outputs equal arcvae_dec_viterbi's.  Monotone is not
+ *   strictly monotone: among sequences whose fp32 scores tie, the rules above decide which are returned; no simple global order on
+ *   sequences is promised.
+ * A row holding a NaN or an infinite logit is outside the contract; it still writes only tokens in [0, V) or pad_token.
+ * ws: caller-owned device scratch for the back pointers, two bytes (u, r') per (step, token, rank) of a row IN FLIGHT: the kernel
+ *   runs at most ARCVAE_KBEST_ROWS_IN_FLIGHT workgroups, each looping over rows b = its index, + the grid size, ... and reusing
+ *   its slice, so arcvae_dec_kbest_ws_bytes = min(B, ARCVAE_KBEST_ROWS_IN_FLIGHT) * 2 * max_len * V * K whatever B is. */
+#define ARCVAE_KBEST_ROWS_IN_FLIGHT 1024 /* 256 CUs x 4 workgroups of 256 threads: what the LDS of the V 80 workload admits per CU */
+int arcvae_dec_kbest_ws_bytes(int B, int V, int K, int max_len, long* bytes);
+int arcvae_dec_kbest(const float* dense_logits, const float* lse, int32_t* tokens /*[B,K,max_len]*/, float* scores /*[B,K]*/,
+                     int32_t* lengths /*[B,K]*/, void* ws, long ws_bytes, int B, int V, int K, int max_len, int min_len,
+                     int end_token, int pad_token, float temperature, arcvae_stream_t stream);
 /* EXTENSION (no reference counterpart: the reference decodes greedily) -- top-k / nucleus (top-p) truncated sampling over the dense
  * logits [B*V, V] of arcvae_dec_forward_dense (mode 0); row r = b*V + c holds batch row b's logits after token c.
  * 1 <= vocab_size <= 256, temperature > 0, top_k >= 0 (0 = all V), 0 < top_p <= 1; anything else (NaN included) is ARCVAE_ERR_ARG.

@@ -1,0 +1,438 @@
+// Exact K-best decoding: the K most probable admissible sequences per batch row of the chain the dense decoder table defines, by a
+// list-Viterbi recursion -- an EXTENSION beside chain.hip with no reference behaviour to match.  The contract (lists, candidate
+// order, result order, outputs, exactness) is stated once, in include/arcvae_hip.h; tests/kbest_ref.py restates it in NumPy.
+// Step term and score are chain.hip's: lp(u, v) = fl(fl(x[b*V+u, v] * inv_temp) - lse[b*V+u]), a candidate = fl(s + lp).
+//
+// Kernel: a bounded grid of 256-thread workgroups, one batch row in flight per workgroup, rows b = blockIdx.x, + gridDim.x, ...
+// Both list buffers live in LDS, rank-major ([K][V4], V4 = V rounded up to 4; empty = -inf).  The row's step terms are computed
+// once into LDS, TRANSPOSED ([v][V4]: a column's terms are contiguous in u), when they fit beside the lists in 64 KB, and read
+// from the table through L2 otherwise.
+// A step is, per column v, a V-way merge of sorted lists: adding lp(u, v) keeps a_{t-1}[u] sorted, so only the list heads compete.
+// A GROUP of GL lanes merges one column: 16 lanes (one DPP row; four columns per wave, sixteen per pass of the workgroup) for
+// V <= 128, a whole wave above.  Lane l of the group holds the heads of u = l, l + GL, ..: J = ceil(V / GL) heads in registers.
+// A head is the packed key (order-preserving integer image of its score, 255 - u, r'): the maximum of the keys IS the contract's
+// (score desc, u asc, r' asc) -- a list offers its ranks in order -- so any reduction order gives the same winner.  Each of the K
+// rounds takes the lane's best head, an all-reduce maximum over the group (four DPP row rotations; the wave-wide group combines
+// its four rows through scalar registers), and the one lane whose key is the maximum advances that head with one LDS read.
+// The winner's score and origin arrive in every lane with the key; lane r mod 16 keeps rank r and, after the rounds, writes it
+// to the new list with its back pointer (two bytes (u, r') per (t, v, rank), in the workgroup's slice of the caller's scratch).
+// The wave that holds the end column merges that column's list into the running result (K entries in LDS: score, step, last
+// token and rank) at every step t >= min_len; after the last step wave 0 merges the final lists the same V-way way, then into the
+// result.  Both are stable merges with the earlier arrival first, which is the contract's stable sort of all arrivals.  The
+// back-trace is one thread per returned sequence; every pointer is clamped when followed, so a row outside the contract stays
+// inside [0, V).
+#include "common.h"
+
+namespace {
+
+constexpr int KB_MAX_V = 256;
+constexpr int KB_MAX_K = 32;
+constexpr int KB_THREADS = 256;
+constexpr int KB_WAVES = KB_THREADS / 64;
+constexpr int KB_SMALL_V = 128;              // largest V merged by groups of 16 lanes (8 heads per lane)
+constexpr int KB_STAGE_LDS = 64 * 1024;      // the step terms are staged when everything fits in this much LDS
+// LDS (dwords): lse [256] | result score, step, (token << 8 | rank): [2][32] each | arriving list: score, (token << 8 | rank): [32]
+// each | list A [K][V4] | list B [K][V4] | step terms [V][V4] when staged
+constexpr int KB_OFF_RES_S = 256, KB_OFF_RES_T = 320, KB_OFF_RES_VR = 384, KB_OFF_ARR_S = 448, KB_OFF_ARR_VR = 480, KB_OFF_LIST = 512;
+
+struct KbestPlan {
+    int GL, J;         // lanes per column, heads per lane: (J - 1) * GL < V <= J * GL
+    bool staged;
+    unsigned lds;      // dynamic LDS bytes
+};
+
+KbestPlan kbest_plan(int V, int K) {
+    KbestPlan p;
+    const int V4 = (V + 3) & ~3;
+    p.GL = V <= KB_SMALL_V ? 16 : 64;
+    p.J = ceil_div(V, p.GL);
+    const unsigned base = (unsigned)(KB_OFF_LIST + 2 * K * V4) * 4u, tab = (unsigned)(V * V4) * 4u;
+    p.staged = base + tab <= (unsigned)KB_STAGE_LDS;           // (never above V 124; always up to V 96)
+    p.lds = base + (p.staged ? tab : 0u);
+    return p;
+}
+
+// Order-preserving integer image of a float: a > b (neither a NaN) <=> key(a) > key(b); key(-inf) is an empty head's.
+__device__ __forceinline__ unsigned kb_key(float f) {
+    const unsigned b = __float_as_uint(f);
+    return (b & 0x80000000u) ? ~b : (b | 0x80000000u);
+}
+__device__ __forceinline__ float kb_unkey(unsigned k) { return __uint_as_float((k & 0x80000000u) ? (k & 0x7fffffffu) : ~k); }
+constexpr unsigned KB_KEY_EMPTY = 0x007fffffu;
+
+template <int CTRL>
+__device__ __forceinline__ unsigned long long kb_max_dpp(unsigned long long k) {
+    const unsigned lo = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)k, CTRL, 0xf, 0xf, false);
+    const unsigned hi = (unsigned)__builtin_amdgcn_update_dpp(0, (int)(unsigned)(k >> 32), CTRL, 0xf, 0xf, false);
+    const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+    return o > k ? o : k;
+}
+
+// The maximum of k over the lane's group, in every lane of it: rotations by 1, 2, 4, 8 inside the rows of 16 lanes; the
+// wave-wide group then combines lane 0 of its four rows (uniform).
+template <int GL>
+__device__ __forceinline__ unsigned long long kb_group_max(unsigned long long k) {
+    k = kb_max_dpp<0x121>(k);                                  // row_ror:1
+    k = kb_max_dpp<0x122>(k);                                  // row_ror:2
+    k = kb_max_dpp<0x124>(k);                                  // row_ror:4
+    k = kb_max_dpp<0x128>(k);                                  // row_ror:8
+    if (GL == 64) {
+        unsigned long long m = 0;
+#pragma unroll
+        for (int row = 0; row < 64; row += 16) {
+            const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)k, row);
+            const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(k >> 32), row);
+            const unsigned long long o = ((unsigned long long)hi << 32) | lo;
+            m = o > m ? o : m;
+        }
+        k = m;
+    }
+    return k;
+}
+
+// What one wave wrote to LDS is read by its other lanes: the hardware keeps a wave's LDS operations in order; this keeps the
+// compiler from moving them.
+__device__ __forceinline__ void kb_wave_lds_order() {
+    __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
+    __builtin_amdgcn_wave_barrier();
+    __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
+}
+
+// The step terms of u = l, l + GL, .. into column v (0 where the group is idle or u >= V: those heads are empty).
+template <int GL, int J, bool STAGED>
+__device__ __forceinline__ void kb_terms(float (&term)[J], const float* tab, const float* __restrict__ x, const float* ls, int v,
+                                         bool active, int V, int V4, int l, float inv_temp) {
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int u = j * GL + l;
+        term[j] = 0.f;
+        if (active && u < V) {
+            if (STAGED) {
+                term[j] = tab[v * V4 + u];
+            } else {
+                const float a = x[(long)u * V + v] * inv_temp;
+                term[j] = a - ls[u];
+            }
+        }
+    }
+}
+
+// A value the compiler has to treat as computed, not as loaded: a choice among term[0 .. J-1] by the winner's j otherwise becomes
+// one load at a variable index, which moves the whole array from registers to scratch memory.
+__device__ __forceinline__ float kb_in_register(float x) {
+    asm("" : "+v"(x));
+    return x;
+}
+
+// The first K of the V-way merge of the lists prev[.][u] + term(u), per group, whole wave: lane l < 16 of the group returns the
+// ranks l (slot 0) and l + 16 (slot 1): score (-inf = empty) and origin (u << 8 | r').
+template <int GL, int J>
+__device__ __forceinline__ void kb_merge(const float* prev, bool active, int V, int V4, int K, const float (&term)[J], int l,
+                                         float (&out_s)[2], int (&out_o)[2]) {
+    unsigned hk[J];                                            // the heads: key of the score, and the rank offered
+    int hr[J];
+#pragma unroll
+    for (int j = 0; j < J; ++j) {
+        const int u = j * GL + l;
+        hk[j] = KB_KEY_EMPTY;
+        hr[j] = 0;
+        if (active && u < V) hk[j] = kb_key(prev[u] + term[j]);               // rank 0; -inf where empty, the end token included
+    }
+    out_s[0] = out_s[1] = -INFINITY;
+    out_o[0] = out_o[1] = 0;
+    for (int r = 0; r < K; ++r) {
+        unsigned bk = hk[0];
+        int bj = 0, br = hr[0];
+        float bt = kb_in_register(term[0]);
+#pragma unroll
+        for (int j = 1; j < J; ++j) {
+            const float tj = kb_in_register(term[j]);
+            if (hk[j] > bk) {                                  // (strict: the lowest u of a lane's ties)
+                bk = hk[j];
+                bj = j;
+                br = hr[j];
+                bt = tj;
+            }
+        }
+        const int bu = bj * GL + l;
+        const unsigned long long mine = ((unsigned long long)bk << 32) | (unsigned)(((255 - bu) << 8) | br);
+        const unsigned long long top = kb_group_max<GL>(mine);
+        const bool cand = (unsigned)(top >> 32) > KB_KEY_EMPTY;
+        if (!__any(cand)) break;                               // (wave-uniform) no group has a head left
+        if (cand && l == (r & 15)) {
+            const unsigned w = (unsigned)top;
+            const float ws = kb_unkey((unsigned)(top >> 32));
+            const int wo = (int)(((255u - ((w >> 8) & 0xffu)) << 8) | (w & 0xffu));
+            if (r < 16) {
+                out_s[0] = ws;
+                out_o[0] = wo;
+            } else {
+                out_s[1] = ws;
+                out_o[1] = wo;
+            }
+        }
+        const bool win = cand && mine == top;                  // one lane per group: u is part of the key
+        const int nr = br + 1;
+        float s = -INFINITY;
+        if (win && nr < K) s = prev[nr * V4 + bu];
+        const unsigned nk = kb_key(s + bt);
+#pragma unroll
+        for (int j = 0; j < J; ++j)
+            if (win && j == bj) {
+                hk[j] = nk;
+                hr[j] = nr;
+            }
+    }
+}
+
+// Stable merge of the running result (K entries, sorted) with an arriving sorted list, the result's entries first on ties, into
+// the other result buffer: an entry's new position is its own index plus the entries of the other list that precede it.  Whole
+// wave; lanes 0 .. K-1 place the result's entries, lanes 32 .. 32+K-1 the arrivals.
+__device__ __forceinline__ void kb_arrive(const float* rs, const int* rt, const int* rvr, float* ns, int* nt, int* nvr,
+                                          const float* as, const int* avr, int at, int K, int lane) {
+    if (lane < K) {
+        const float s = rs[lane];
+        int pos = lane;
+        for (int j = 0; j < K; ++j) pos += as[j] > s ? 1 : 0;
+        if (pos < K) {
+            ns[pos] = s;
+            nt[pos] = rt[lane];
+            nvr[pos] = rvr[lane];
+        }
+    } else if (lane >= 32 && lane < 32 + K) {
+        const int j = lane - 32;
+        const float s = as[j];
+        int pos = j;
+        for (int i = 0; i < K; ++i) pos += rs[i] >= s ? 1 : 0;
+        if (pos < K) {
+            ns[pos] = s;
+            nt[pos] = at;
+            nvr[pos] = avr[j];
+        }
+    }
+}
+
+template <int GL, int J, bool STAGED>
+__global__ __launch_bounds__(KB_THREADS) void kbest_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
+                                                           uint8_t* bp, int32_t* tokens, float* scores, int32_t* lengths, int B,
+                                                           int V, int K, int max_len, int min_len, int end_token, int pad_token,
+                                                           float inv_temp) {
+    constexpr int GPW = 64 / GL, NG = KB_WAVES * GPW;          // groups per wave; columns per pass of the workgroup
+    extern __shared__ __align__(16) float smem[];
+    const int V4 = (V + 3) & ~3;
+    float* ls = smem;
+    float* res_s = smem + KB_OFF_RES_S;
+    int* res_t = (int*)(smem + KB_OFF_RES_T);
+    int* res_vr = (int*)(smem + KB_OFF_RES_VR);
+    float* arr_s = smem + KB_OFF_ARR_S;
+    int* arr_vr = (int*)(smem + KB_OFF_ARR_VR);
+    float* la = smem + KB_OFF_LIST;
+    float* lb = la + K * V4;
+    float* tab = lb + K * V4;
+    const int tid = threadIdx.x, lane = tid & 63, l = lane & (GL - 1);
+    const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
+    const int grp = wave * GPW + lane / GL;                    // the group's column within a pass
+    uint8_t* bpb = bp + (long)blockIdx.x * 2 * max_len * V * K;          // this workgroup's slice: [max_len][V][K][2]
+
+    for (int b = blockIdx.x; b < B; b += gridDim.x) {
+        const float* x = logits + (long)b * V * V;
+        if (tid < V) ls[tid] = lse[(long)b * V + tid];
+        for (int i = tid; i < 2 * K * V4; i += KB_THREADS) la[i] = -INFINITY;      // both lists empty
+        if (tid < 2 * KB_MAX_K) {
+            res_s[tid] = -INFINITY;
+            res_t[tid] = 0;
+            res_vr[tid] = 0;
+        }
+        __syncthreads();
+        if (STAGED) {
+            for (int i = tid; i < V * V; i += KB_THREADS) {
+                const int u = i / V, v = i - u * V;
+                const float a = x[i] * inv_temp;
+                tab[v * V4 + u] = a - ls[u];
+            }
+            __syncthreads();
+        }
+        // step 0: a_0[v] = [fl(0 + lp(0, v))]; the end column goes straight to the (empty) result
+        if (tid < V) {
+            float lp;
+            if (STAGED) {
+                lp = tab[tid * V4];
+            } else {
+                const float a = x[tid] * inv_temp;
+                lp = a - ls[0];
+            }
+            const float s = 0.f + lp;
+            if (tid == end_token) {
+                if (min_len == 0) {
+                    res_s[0] = s;
+                    res_vr[0] = end_token << 8;
+                }
+            } else {
+                la[tid] = s;
+            }
+        }
+        __syncthreads();
+        float* cur = la;
+        float* nxt = lb;
+        int rc = 0;                                            // the result buffer that is current
+        for (int t = 1; t < max_len; ++t) {
+            for (int v0 = 0; v0 < V; v0 += NG) {
+                const int v = v0 + grp;
+                const bool active = v < V;
+                float term[J], os[2];
+                int oo[2];
+                kb_terms<GL, J, STAGED>(term, tab, x, ls, v, active, V, V4, l, inv_temp);
+                kb_merge<GL, J>(cur, active, V, V4, K, term, l, os, oo);
+                if (active && l < 16) {
+#pragma unroll
+                    for (int h = 0; h < 2; ++h) {
+                        const int r = l + 16 * h;
+                        if (r < K) {
+                            nxt[r * V4 + v] = v == end_token ? -INFINITY : os[h];  // the end token never continues
+                            const long o = (((long)t * V + v) * K + r) * 2;
+                            bpb[o] = (uint8_t)(oo[h] >> 8);
+                            bpb[o + 1] = (uint8_t)oo[h];
+                            if (v == end_token) {
+                                arr_s[r] = os[h];
+                                arr_vr[r] = (end_token << 8) | r;
+                            }
+                        }
+                    }
+                }
+                const int e = end_token - v0;                  // this wave holds the end column in this pass (uniform)
+                if (t >= min_len && e >= 0 && e < NG && e / GPW == wave) {
+                    kb_wave_lds_order();
+                    const int o = rc * KB_MAX_K, n = (rc ^ 1) * KB_MAX_K;
+                    kb_arrive(res_s + o, res_t + o, res_vr + o, res_s + n, res_t + n, res_vr + n, arr_s, arr_vr, t, K, lane);
+                }
+            }
+            if (t >= min_len) rc ^= 1;
+            __syncthreads();
+            float* sw = cur;
+            cur = nxt;
+            nxt = sw;
+        }
+        // the lists a_{max_len-1}[v], v != end_token (that column is empty): one more V-way merge, with nothing added
+        if (wave == 0) {
+            const bool active = lane < GL;                     // the wave's first group
+            float term[J], os[2];
+            int oo[2];
+#pragma unroll
+            for (int j = 0; j < J; ++j) term[j] = 0.f;
+            kb_merge<GL, J>(cur, active, V, V4, K, term, l, os, oo);
+            if (active && l < 16) {
+#pragma unroll
+                for (int h = 0; h < 2; ++h) {
+                    const int r = l + 16 * h;
+                    if (r < K) {
+                        arr_s[r] = os[h];
+                        arr_vr[r] = oo[h];
+                    }
+                }
+            }
+            kb_wave_lds_order();
+            const int o = rc * KB_MAX_K, n = (rc ^ 1) * KB_MAX_K;
+            kb_arrive(res_s + o, res_t + o, res_vr + o, res_s + n, res_t + n, res_vr + n, arr_s, arr_vr, max_len - 1, K, lane);
+        }
+        rc ^= 1;
+        __syncthreads();
+        // back-trace: one thread per returned sequence
+        if (tid < K) {
+            const float s = res_s[rc * KB_MAX_K + tid];
+            int32_t* out = tokens + ((long)b * K + tid) * max_len;
+            int n = 0;
+            if (s > -INFINITY) {                               // (a NaN counts as empty)
+                n = min(max(res_t[rc * KB_MAX_K + tid], 0), max_len - 1) + 1;
+                const int vr = res_vr[rc * KB_MAX_K + tid];
+                int v = min(vr >> 8, V - 1), r = min(vr & 0xff, K - 1);
+                out[n - 1] = v;
+                for (int t = n - 1; t >= 1; --t) {
+                    const long o = (((long)t * V + v) * K + r) * 2;
+                    v = min((int)bpb[o], V - 1);
+                    r = min((int)bpb[o + 1], K - 1);
+                    out[t - 1] = v;
+                }
+            }
+            for (int t = n; t < max_len; ++t) out[t] = pad_token;
+            scores[(long)b * K + tid] = n > 0 ? s : -INFINITY;
+            lengths[(long)b * K + tid] = n;
+        }
+        __syncthreads();                                       // the next row reuses the LDS and the slice
+    }
+}
+
+bool kbest_dims_ok(int B, int V, int K, int max_len) {
+    return B > 0 && V >= 1 && V <= KB_MAX_V && K >= 1 && K <= KB_MAX_K && max_len >= 1;
+}
+
+long kbest_ws_need(int B, int V, int K, int max_len) {
+    return (long)(B < ARCVAE_KBEST_ROWS_IN_FLIGHT ? B : ARCVAE_KBEST_ROWS_IN_FLIGHT) * 2 * max_len * V * K;
+}
+
+struct KbestArgs {
+    const float* logits;
+    const float* lse;
+    uint8_t* bp;
+    int32_t* tokens;
+    float* scores;
+    int32_t* lengths;
+    int B, V, K, max_len, min_len, end_token, pad_token;
+    float inv_temp;
+};
+
+template <int GL, int J, bool STAGED>
+void kbest_launch(const KbestArgs& a, unsigned lds, int grid, hipStream_t stream) {
+    // > 64 KB of dynamic LDS has to be allowed per kernel; set on every call (idempotent, no host state kept)
+    (void)hipFuncSetAttribute((const void*)kbest_kernel<GL, J, STAGED>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
+    hipLaunchKernelGGL((kbest_kernel<GL, J, STAGED>), dim3(grid), dim3(KB_THREADS), lds, stream, a.logits, a.lse, a.bp, a.tokens,
+                       a.scores, a.lengths, a.B, a.V, a.K, a.max_len, a.min_len, a.end_token, a.pad_token, a.inv_temp);
+}
+
+// J <= 6 (V <= 96) is always staged, the wave-wide groups (V > 128) never are.
+template <int J>
+void kbest_launch_small(const KbestArgs& a, const KbestPlan& pl, int grid, hipStream_t stream) {
+    if constexpr (J > 6) {
+        if (!pl.staged) {
+            kbest_launch<16, J, false>(a, pl.lds, grid, stream);
+            return;
+        }
+    }
+    kbest_launch<16, J, true>(a, pl.lds, grid, stream);
+}
+
+}  // namespace
+
+extern "C" int arcvae_dec_kbest_ws_bytes(int B, int V, int K, int max_len, long* bytes) {
+    if (!bytes || !kbest_dims_ok(B, V, K, max_len)) return ARCVAE_ERR_ARG;
+    *bytes = kbest_ws_need(B, V, K, max_len);
+    return ARCVAE_OK;
+}
+
+extern "C" int arcvae_dec_kbest(const float* dense_logits, const float* lse, int32_t* tokens, float* scores, int32_t* lengths,
+                                void* ws, long ws_bytes, int B, int V, int K, int max_len, int min_len, int end_token,
+                                int pad_token, float temperature, hipStream_t stream) {
+    if (!dense_logits || !lse || !tokens || !scores || !lengths || !ws || !kbest_dims_ok(B, V, K, max_len)) return ARCVAE_ERR_ARG;
+    if (end_token < 0 || end_token >= V || min_len < 0 || min_len > max_len || pad_token < 0 || pad_token > 255) return ARCVAE_ERR_ARG;
+    if (!(temperature > 0.f && temperature <= 3.402823466e+38f)) return ARCVAE_ERR_ARG;      // finite and > 0 (a NaN compares false)
+    if (ws_bytes < kbest_ws_need(B, V, K, max_len)) return ARCVAE_ERR_ARG;
+    const KbestPlan pl = kbest_plan(V, K);
+    const int grid = B < ARCVAE_KBEST_ROWS_IN_FLIGHT ? B : ARCVAE_KBEST_ROWS_IN_FLIGHT;
+    const KbestArgs a = {dense_logits, lse, (uint8_t*)ws, tokens, scores, lengths, B, V, K, max_len, min_len, end_token, pad_token,
+                         1.0f / temperature};
+    if (pl.GL == 64) {
+        if (pl.J == 3) kbest_launch<64, 3, false>(a, pl.lds, grid, stream);
+        else kbest_launch<64, 4, false>(a, pl.lds, grid, stream);
+    } else {
+        switch (pl.J) {
+            case 1: kbest_launch_small<1>(a, pl, grid, stream); break;
+            case 2: kbest_launch_small<2>(a, pl, grid, stream); break;
+            case 3: kbest_launch_small<3>(a, pl, grid, stream); break;
+            case 4: kbest_launch_small<4>(a, pl, grid, stream); break;
+            case 5: kbest_launch_small<5>(a, pl, grid, stream); break;
+            case 6: kbest_launch_small<6>(a, pl, grid, stream); break;
+            case 7: kbest_launch_small<7>(a, pl, grid, stream); break;
+            default: kbest_launch_small<8>(a, pl, grid, stream); break;
+        }
+    }
+    return arcvae_launch_status();
+}

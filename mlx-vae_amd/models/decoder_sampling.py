@@ -9,7 +9,7 @@ sampling the reference marks TODO (decoder_sampling.py:115-116): an extension wi
 `generate_beam` (beam search with scores, csrc/beam.hip); `decoder.sequence_log_prob` scores given sequences; and
 `sample=True` with `top_k` / `top_p` (truncated sampling, csrc/sample.hip); and `generate_map` / `token_marginals` /
 `length_distribution`: the exact most probable sequence and the exact per-step token and length distributions of the chain the
-dense table defines (csrc/chain.hip)."""
+dense table defines (csrc/chain.hip); and `generate_kbest`: the exact K most probable sequences of that chain (csrc/kbest.hip)."""
 from __future__ import annotations
 
 import torch
@@ -255,6 +255,37 @@ class MLXAutoregressiveDecoderSampling:
              T, int(min_length), self.end_token, self.pad_token, float(temperature), stream_ptr())
         if early_stopping:
             tokens = tokens[:, :int(lengths.max().item())].contiguous()
+        return tokens, scores
+
+    def generate_kbest(self, z, conditions, max_length: int = 80, num_best: int = 4, temperature: float = 1.0, min_length: int = 0,
+                       early_stopping: bool = True):
+        """Extension (absent in the reference): the num_best MOST PROBABLE sequences per row under log_softmax(logits / T), exactly
+        -- a list-Viterbi recursion over the dense table (include/arcvae_hip.h arcvae_dec_kbest) -> (tokens [B, K, L] int32,
+        scores [B, K] float32, descending).  z is accepted and unused (Q2).  Sequences, min_length and padding as in generate_map;
+        the K sequences of a row are pairwise distinct, rank 0 is generate_map's, and no rank is below generate_beam's at
+        beam_width = num_best.  A slot that no sequence fills (num_best above the number of admissible sequences) has score -inf
+        and pad tokens.  early_stopping: L = the longest returned sequence (at least 1); otherwise L = max_length.  Each score
+        equals decoder.sequence_log_prob of its tokens bit for bit; exp(scores).sum(1) is the probability mass the list covers."""
+        import ctypes as C
+        K, T = int(num_best), int(max_length)
+        if not 1 <= K <= 32:
+            raise ValueError("num_best must lie in [1, 32]")
+        if T < 1 or not 0 <= int(min_length) <= T:
+            raise ValueError("need max_length >= 1 and 0 <= min_length <= max_length")
+        if not 0 <= self.pad_token <= 255:
+            raise ValueError("exact decoding needs 0 <= pad_token <= 255")
+        logits, lse, B = self._chain_table(conditions, T, temperature)
+        V, dev = self.decoder.vocab_size, self.decoder.store.device
+        nbytes = C.c_long(0)
+        call("arcvae_dec_kbest_ws_bytes", B, V, K, T, C.byref(nbytes))
+        scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
+        tokens = torch.empty(B, K, T, dtype=torch.int32, device=dev)
+        scores = torch.empty(B, K, dtype=torch.float32, device=dev)
+        lengths = torch.empty(B, K, dtype=torch.int32, device=dev)
+        call("arcvae_dec_kbest", ptr(logits), ptr(lse), ptr(tokens), ptr(scores), ptr(lengths), ptr(scratch), nbytes.value, B, V,
+             K, T, int(min_length), self.end_token, self.pad_token, float(temperature), stream_ptr())
+        if early_stopping:
+            tokens = tokens[:, :, :max(int(lengths.max().item()), 1)].contiguous()
         return tokens, scores
 
     def token_marginals(self, conditions, max_length: int = 80, temperature: float = 1.0) -> torch.Tensor:
