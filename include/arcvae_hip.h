@@ -252,7 +252,8 @@ int arcvae_enc_lstm_backward_fused(const float* const* Wx, const float* const* W
  * (ARCVAE_GEMM_SPLIT3: fp32-class accuracy, for the MFMA-bound regime beside the tiled sweeps); bit 7 = throughput mode (one bf16 product per GEMM step instead of
  * the six of the split form: not a parity path); bit 11 = h_oct / dG_oct are the sweeps' three-plane operand rings hseq_t /
  * dG_t with ALL T time slots (arcvae_enc_lstm_operand_slots == T): the per-layer GEMMs read the planes directly (transposing
- * LDS reads, no f32 loads, no re-splitting; needs B % 32 == 0).  The token-table path is linear in dtable_ws, so a
+ * LDS reads, no f32 loads, no re-splitting; needs B % 32 == 0); bit 13 = `last` folds with arcvae_table_fold instead of
+ * arcvae_table_finalize (the caller guarantees that no other launch updates dEmb, dWx[0] or dbias[0] meanwhile).  The token-table path is linear in dtable_ws, so a
  * time range may be given its own workspace and both `first` and `last` (zero, accumulate, fold) on any stream. */
 int arcvae_enc_lstm_wgrad(const int32_t* x_tb, const float* emb, const float* Wx0, const float* hseq,
                           const float* dG, float* dtable_ws, float* onehot_ws, float* dEmb, float* const* dWx,
@@ -597,6 +598,14 @@ int arcvae_zero(float* x, int rows, int cols, int ld, arcvae_stream_t stream);
  * dEmb [V,E] += dT . Wx0[:, :E];  dWx0[:, :E] += dT^T . emb (row stride ldw);  db0 [4H] += colsum(dT). */
 int arcvae_table_finalize(const float* dT, const float* Wx0, int ldw, const float* emb, float* dEmb, float* dWx0,
                           float* db0, int V, int E, int G, arcvae_stream_t stream);
+/* The same three "+=" (same argument checks) on the exact-f32 MFMA forms with ONE owner per output element: no atomics,
+ * a few KB of LDS, two runs bit-identical.  THE CALLER GUARANTEES that no other launch updates dEmb, dWx0[:, :E] or db0
+ * while this one runs (arcvae_table_finalize's atomics allowed two folds at once; this one's plain "+=" does not).
+ * dT2 (optional): a second table, the fold reads dT + dT2 (both 16-byte aligned).  [g_lo, g_hi) (both 0: none; else
+ * multiples of 32 within [0, G]): columns of the table known to be zero -- they are not read (a gap in K for dEmb) and
+ * rows [g_lo, g_hi) of dWx0 / db0 are not touched.  Columns E .. ldw-1 of dWx0 are never touched. */
+int arcvae_table_fold(const float* dT, const float* dT2, const float* Wx0, int ldw, const float* emb, float* dEmb,
+                      float* dWx0, float* db0, int V, int E, int G, int g_lo, int g_hi, arcvae_stream_t stream);
 /* Device-side gates (no reference counterpart): cross-stream ordering by a one-wave polling kernel instead of an
  * event wait, because a hardware queue blocked on an event slows every dependent dispatch of the chain that is
  * running.  wait: returns once (int)(*flag - ((*steps) * stride + offset)) >= 0 (steps may be

@@ -33,6 +33,7 @@ DEC_PART_TAIL = 4096  # ... fc_out only (layers 1 .. L-1 by arcvae_dense_stack_f
 DEC_NO_GPRE = 1024   # arcvae_dec_forward_dense mode bit: forward only, pre-activations not kept (fused GEMM + cell)
 WGRAD_BF16 = 128     # arcvae_enc_lstm_wgrad parts bit
 WGRAD_QUIET = 512    # arcvae_enc_lstm_wgrad parts bit 9: the per-layer GEMMs on the quiet split-bf16 kernel
+WGRAD_FOLD = 8192    # arcvae_enc_lstm_wgrad parts bit 13: `last` folds with arcvae_table_fold (alone on its outputs)
 
 _vp = C.c_void_p
 _i = C.c_int
@@ -113,6 +114,7 @@ SIGNATURES = {
     "arcvae_debug_occupy": [_i, _i, _i, _i, _vp],
     "arcvae_zero": [_vp, _i, _i, _i, _vp],
     "arcvae_table_finalize": [_vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _vp],
+    "arcvae_table_fold": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _vp, _i, _i, _i, _i, _i, _vp],
     "arcvae_gate_wait": [_vp, _vp, C.c_uint, C.c_uint, _i, C.c_uint, _vp, _vp],
     "arcvae_gate_set": [_vp, C.c_uint, _i, _vp],
     "arcvae_tile_weights": [_pp, _pp, _ip, _ip, _i, _i, _vp],

@@ -547,6 +547,11 @@ class SegmentRunner:
 
 
 WGRAD_QUIET_DEFAULT = "1"
+# ARCVAE_TAIL_FORM: what main and side carry behind the bs-64 BPTT sweep's last tick (_encoder_backward_gated).  0: every
+# chunk folds its own token table, main forms the last chunk's; 1: side accumulates one table and folds it once, main
+# forms the last chunk's layer GEMMs behind its own sweep with no gate (bs 64: 0.8963 -> 0.8855 ms, five alternations;
+# boundary 0.7 stays ahead of 0.75 / 0.8 / 0.85 in this form too: profiles/tail_step_ab.txt).
+TAIL_FORM_DEFAULT = "1"
 
 
 def wgrad_quiet() -> bool:
@@ -834,6 +839,13 @@ def _encoder_backward_gated(plan: EncoderBackwardPlan, ws: Workspace, aux, aux2,
     # side's tail was a chain of four kernels (~100 us).  Needs the one-hot rows from arcvae_enc_prologue (persistent
     # forward path).  ARCVAE_TABLE_ON_MAIN=0: round 1's accumulate-on-side form.
     own_tables = table_on_side and _tables_on_main(plan, ws)
+    # ARCVAE_TAIL_FORM=1, quiet regime only: main and side swap what they carry in the tail.  The fold is linear in the
+    # table, so side accumulates ONE table over the chunks (first / last as the chunks say) and folds it once, alone on
+    # its outputs (arcvae_table_fold: no atomics) -- and main, which needs no gate behind its own sweep, forms the last
+    # chunk's layer GEMMs, the launch that ends the step.  aux's last segment keeps its wait and its R signal and forms
+    # nothing; every gate word moves as in form 0.
+    tail_form1 = (own_tables and bool(getattr(plan, "quiet", False)) and not wx_on_side
+                  and os.environ.get("ARCVAE_TAIL_FORM", TAIL_FORM_DEFAULT) == "1")
 
     def pre_zeroed() -> int:
         # parts bit 8: this step's prologue has zeroed both token tables and each is used once (two chunks): no zero-fill
@@ -851,7 +863,10 @@ def _encoder_backward_gated(plan: EncoderBackwardPlan, ws: Workspace, aux, aux2,
         for c, (s0, s1, _t_lo, _t_hi, _first, _last) in enumerate(plan.chunks):
             plan.sweep(s0, s1, g.word(g.P) if c > 0 else g.word(g.H), c)   # chunk 0's first launch: "the sweep has started"
         g.signal(g.P, g.STRIDE - nc)
-        if own_tables:
+        if tail_form1:
+            _s0, _s1, t_lo_l, t_hi_l, first_l, last_l = plan.chunks[-1]
+            plan.wgrad(t_lo_l, t_hi_l, first_l, last_l, 1)   # (the plan adds the quiet bit; the table is side's)
+        elif own_tables:
             _s0, _s1, t_lo_l, t_hi_l, _f, _l = plan.chunks[-1]
             plan.wgrad(t_lo_l, t_hi_l, True, True, 2 | 32 | pre_zeroed(), table=getattr(ws, "dtable1", None))
         if epilogue is not None:
@@ -882,8 +897,9 @@ def _encoder_backward_gated(plan: EncoderBackwardPlan, ws: Workspace, aux, aux2,
             if c == 0 and not heads_early:
                 plan.heads(2)
                 g.signal(g.HG, 1)   # (every gated step, single process too: HG stays in lockstep with side's ticket counter)
-            plan.wgrad(t_lo, t_hi, first, last,
-                       8 if wx_on_side else (1 if (table_on_side or (last and tail_on_side)) else 3))
+            if not (tail_form1 and last):   # form 1: main forms the last chunk's layer GEMMs behind its own sweep
+                plan.wgrad(t_lo, t_hi, first, last,
+                           8 if wx_on_side else (1 if (table_on_side or (last and tail_on_side)) else 3))
             if c == max(nc - 2, 0):
                 g.signal(g.Q, 1)
             if last:
@@ -895,7 +911,10 @@ def _encoder_backward_gated(plan: EncoderBackwardPlan, ws: Workspace, aux, aux2,
             else:
                 g.wait(g.Q, g.NS, 1, 1)
                 g.wait(g.P, g.NS, g.STRIDE, g.STRIDE, advance=True)
-            if own_tables:   # this chunk's own table (not the last chunk's: main forms that one)
+            if tail_form1:   # one table over the chunks, one fold behind the last: nothing else updates its outputs then
+                zeroed = 256 if (first and ws is not None and getattr(ws, "tables_zeroed", False)) else 0
+                plan.wgrad(t_lo, t_hi, first, last, 2 | 32 | zeroed | (_lib.WGRAD_FOLD if last else 0))
+            elif own_tables:   # this chunk's own table (not the last chunk's: main forms that one)
                 plan.wgrad(t_lo, t_hi, True, True, ((4 if wx_on_side else 0) | (0 if last else 2)) | 32 | pre_zeroed())
             else:
                 plan.wgrad(t_lo, t_hi, first, last, 6 if wx_on_side else 2)

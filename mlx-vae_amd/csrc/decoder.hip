@@ -590,7 +590,10 @@ extern "C" int arcvae_dec_backward_dense(const float* emb, const float* const* W
         hipLaunchKernelGGL(dec_wc_reduce_kernel, dim3(ceil_div(G * C, 4)), dim3(256), 0, stream, wcpart, dWx[0],
                            V, G, E, C);
     // dEmb += dTableD . Wx0[:, :E];  dWx0[:, :E] += dTableD^T . Emb (ld E + C);  dbias_0 += colsum(dTableD)
-    rc = arcvae_table_finalize(dtableD, Wx[0], E + C, emb, dEmb, dWx[0], dbias[0], V, E, G, stream);
+    // (this fold is alone on its outputs: one owner per element.  dec_l0_bwd_kernel stores the forget quarter [H, 2H) of
+    // dTableD as zeros for every (v, unit), so with the dead-gate skip on it is a dead range: not read, "+= 0" not done)
+    rc = arcvae_table_fold(dtableD, nullptr, Wx[0], E + C, emb, dEmb, dWx[0], dbias[0], V, E, G, skipf ? H : 0, skipf ? 2 * H : 0,
+                           stream);
     if (rc) return rc;
     return arcvae_launch_status();
 }

@@ -3944,6 +3944,8 @@ extern "C" int arcvae_dense_stack_backward(const float* gates, const float* dh_t
 //   GEMM keeps its kernel
 //   bit 11 = h_oct / dG_oct are the three-plane operand rings hseq_t / dG_t with all T slots: GEMMs from the planes
 //   bit 12 (with 11) = those rings are scratch: this call first splits dG / h of its time range into them (mid-size batches)
+//   bit 13 = `last` folds with arcvae_table_fold (no atomics): the caller guarantees that nothing else updates dEmb,
+//   dWx[0] or dbias[0] while this call's fold runs
 //   onehot_ws [T*B, roundup(V,4)] workspace: one-hot token rows, written when `first` != 0 (token-table part)
 extern "C" int arcvae_enc_lstm_wgrad(const int32_t* x_tb, const float* emb, const float* Wx0,
                                      const float* hseq, const float* dG, float* dtable_ws, float* onehot_ws,
@@ -4065,6 +4067,8 @@ extern "C" int arcvae_enc_lstm_wgrad(const int32_t* x_tb, const float* emb, cons
             if (rc) return rc;
         }
     }
+    if (last && do_table && (parts & 8192))   // bit 13: this fold is alone on its outputs -> one owner per element, no atomics
+        return arcvae_table_fold(dtable_ws, nullptr, Wx0, E, emb, dEmb, dWx[0], dbias[0], V, E, G, 0, 0, stream);
     if (last && do_table)
         return arcvae_table_finalize(dtable_ws, Wx0, E, emb, dEmb, dWx[0], dbias[0], V, E, G, stream);
     return arcvae_launch_status();

@@ -308,6 +308,122 @@ __global__ __launch_bounds__(256) void table_finalize_kernel(const float* __rest
     }
 }
 
+// ---- the same fold on the exact-f32 matrix cores, ONE owner per output element -------------------------------
+// table_finalize_kernel above is bound by what it waits for, not by its 42 MFLOP: up to 74 KB of LDS per block (a block
+// waits for a CU with that much free beside the sweeps and the GEMMs) and one f32 atomic per partial product.  Here the
+// operands go from global memory straight into MFMA fragments (v_mfma_f32_16x16x4_f32 / 32x32x2_f32: bitwise an fmaf
+// chain, the forms of gemm.hip), every output element is written by exactly one lane with a plain "+=", and the only
+// LDS is the 3 KB through which the four waves of a dEmb block add their K slices in wave order: two runs give the same
+// bits, and a block fits on a CU beside whatever is resident.  Block roles by blockIdx.x:
+//   [0, nA)    dEmb : one 16 x 16 tile (table rows x embedding columns); K = 4H in 16-wide chunks dealt round-robin to
+//                     the 4 waves; a lane's fragment is one float4 of dT along K and four Wx0 rows
+//   [nA, ...)  dWx0 : one 32 x 32 tile (gate rows x embedding columns) per WAVE, K = V; both fragments are 128-byte row
+//                     segments.  The waves of tile column 0 also form db0, a lane per column over the rows in order.
+// TWO: the table is dT + dT2, summed as it is loaded.  [g_lo, g_hi) (multiples of 32, or empty): columns of the table the
+// caller knows to be zero -- never read: a gap in K for dEmb, tiles that are not visited for dWx0 / db0.
+constexpr int FOLD_UA = 8;     // dEmb: K chunks in flight per wave (8 x 16 = 128 of K per round of loads)
+constexpr int FOLD_UB = 20;    // dWx0: K pairs in flight per wave (40 table rows per round of loads)
+template <bool TWO>
+__global__ __launch_bounds__(256) void table_fold_kernel(const float* __restrict__ dT, const float* __restrict__ dT2,
+                                                         const float* __restrict__ Wx0, int ldw,
+                                                         const float* __restrict__ emb, float* dEmb, float* dWx0,
+                                                         float* db0, int V, int E, int G, int g_lo, int g_hi, int nA,
+                                                         int etA, int etB) {
+    __shared__ f32x4 red[3][64];
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    int bid = blockIdx.x;
+    if (bid < nA) {                                   // ---- dEmb
+        const int v0 = (bid / etA) * 16, e0 = (bid % etA) * 16;
+        const int m = lane & 15, kq = lane >> 4;
+        const bool vok = v0 + m < V, eok = e0 + m < E;
+        const int gap = g_hi - g_lo, nlive = (G - gap) >> 4;     // live K chunks; chunk i starts at 16 i, stepped over the gap
+        const float* arow = dT + (long)(v0 + m) * G + 4 * kq;
+        const float* arow2 = TWO ? dT2 + (long)(v0 + m) * G + 4 * kq : nullptr;
+        const float* bcol = Wx0 + (long)(4 * kq) * ldw + e0 + m;
+        f32x4 acc = {0.f, 0.f, 0.f, 0.f};
+        for (int i0 = wave; i0 < nlive; i0 += 4 * FOLD_UA) {
+            f32x4 a[FOLD_UA];
+            float b[FOLD_UA][4];
+#pragma unroll
+            for (int u = 0; u < FOLD_UA; ++u) {
+                const int i = i0 + 4 * u;
+                int k0 = i << 4;
+                if (k0 >= g_lo) k0 += gap;
+                a[u] = f32x4{0.f, 0.f, 0.f, 0.f};
+#pragma unroll
+                for (int j = 0; j < 4; ++j) b[u][j] = 0.f;
+                if (i < nlive) {
+                    if (vok) {
+                        a[u] = *reinterpret_cast<const f32x4*>(arow + k0);
+                        if (TWO) a[u] += *reinterpret_cast<const f32x4*>(arow2 + k0);
+                    }
+                    if (eok)
+#pragma unroll
+                        for (int j = 0; j < 4; ++j) b[u][j] = bcol[(long)(k0 + j) * ldw];
+                }
+            }
+#pragma unroll
+            for (int u = 0; u < FOLD_UA; ++u)
+#pragma unroll
+                for (int j = 0; j < 4; ++j) acc = __builtin_amdgcn_mfma_f32_16x16x4f32(a[u][j], b[u][j], acc, 0, 0, 0);
+        }
+        if (wave > 0) red[wave - 1][lane] = acc;
+        __syncthreads();
+        if (wave == 0) {
+            acc = ((acc + red[0][lane]) + red[1][lane]) + red[2][lane];
+            if (eok)
+#pragma unroll
+                for (int r = 0; r < 4; ++r) {
+                    const int v = v0 + 4 * kq + r;
+                    if (v < V) dEmb[(long)v * E + e0 + m] += acc[r];
+                }
+        }
+        return;
+    }
+    bid -= nA;                                        // ---- dWx0 (+ db0): a tile per wave, no barrier below
+    const int t = bid * 4 + wave;
+    if (t >= (G >> 5) * etB) return;
+    const int g0 = (t / etB) * 32, et = t % etB, e0 = et * 32;
+    if (g0 >= g_lo && g0 < g_hi) return;
+    const int m = lane & 31, kh = lane >> 5;
+    const bool eok = e0 + m < E;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    for (int vb = 0; vb < V; vb += 2 * FOLD_UB) {
+        float a[FOLD_UB], b[FOLD_UB];
+#pragma unroll
+        for (int u = 0; u < FOLD_UB; ++u) {
+            const int v = vb + 2 * u + kh;
+            a[u] = 0.f; b[u] = 0.f;
+            if (v < V) {
+                a[u] = dT[(long)v * G + g0 + m];
+                if (TWO) a[u] += dT2[(long)v * G + g0 + m];
+                if (eok) b[u] = emb[(long)v * E + e0 + m];
+            }
+        }
+#pragma unroll
+        for (int u = 0; u < FOLD_UB; ++u)
+            acc = __builtin_amdgcn_mfma_f32_32x32x2f32(a[u], b[u], acc, 0, 0, 0);
+    }
+    if (eok)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int g = g0 + (r & 3) + 8 * (r >> 2) + 4 * kh;
+            dWx0[(long)g * ldw + e0 + m] += acc[r];
+        }
+    if (et == 0 && kh == 0) {   // db0: one lane per column, rows in ascending order -- the sum table_finalize_kernel forms, bit for bit
+        float cs = 0.f;
+#pragma unroll 8
+        for (int v = 0; v < V; ++v) {
+            float x = dT[(long)v * G + g0 + m];
+            if (TWO) x += dT2[(long)v * G + g0 + m];
+            cs += x;
+        }
+        db0[g0 + m] += cs;
+    }
+}
+
 __global__ void transpose_tokens_kernel(const int32_t* __restrict__ src, int32_t* dst, int B, int T) {
     const int i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i < B * T) {
@@ -504,6 +620,30 @@ extern "C" int arcvae_table_finalize(const float* dT, const float* Wx0, int ldw,
     const size_t lds = sizeof(float) * (size_t)max(TF_KS * 128 + TF_ROWS * TF_KS + TF_ROWS * 128, 128 * 16 + 128 * 64);
     hipLaunchKernelGGL(table_finalize_kernel, dim3(nA + nB + nC), dim3(256), lds, stream, dT, Wx0, ldw, emb, dEmb, dWx0,
                        db0, V, E, G, nA, nB, etiles);
+    return arcvae_launch_status();
+}
+
+// The same three "+=" on the exact-f32 matrix cores with one owner per output element (table_fold_kernel): no atomics,
+// 3 KB of LDS.  dT2 (optional): the table is dT + dT2.  [g_lo, g_hi) (optional, both 0: none; multiples of 32): table
+// columns known to be zero -- not read, and rows [g_lo, g_hi) of dWx0 / db0 are not touched.
+// NO other launch may update dEmb, dWx0[:, :E] or db0 while this one runs (plain read-modify-write).
+extern "C" int arcvae_table_fold(const float* dT, const float* dT2, const float* Wx0, int ldw, const float* emb,
+                                 float* dEmb, float* dWx0, float* db0, int V, int E, int G, int g_lo, int g_hi,
+                                 hipStream_t stream) {
+    if (!dT || !Wx0 || !emb || !dEmb || !dWx0 || !db0) return ARCVAE_ERR_ARG;
+    if (V <= 0 || E <= 0 || G <= 0 || (G % 16) != 0 || ldw < E) return ARCVAE_ERR_ARG;
+    if ((G % TF_KS) != 0) return ARCVAE_ERR_ARG;
+    if (g_lo != 0 || g_hi != 0)
+        if (g_lo < 0 || g_hi <= g_lo || g_hi > G || (g_lo % 32) != 0 || (g_hi % 32) != 0) return ARCVAE_ERR_ARG;
+    if ((reinterpret_cast<uintptr_t>(dT) % 16) != 0 || (reinterpret_cast<uintptr_t>(dT2) % 16) != 0) return ARCVAE_ERR_ARG;
+    const int etA = ceil_div(E, 16), etB = ceil_div(E, 32);
+    const int nA = ceil_div(V, 16) * etA, nB = ceil_div((G / 32) * etB, 4);
+    if (dT2)
+        hipLaunchKernelGGL(table_fold_kernel<true>, dim3(nA + nB), dim3(256), 0, stream, dT, dT2, Wx0, ldw, emb, dEmb, dWx0,
+                           db0, V, E, G, g_lo, g_hi, nA, etA, etB);
+    else
+        hipLaunchKernelGGL(table_fold_kernel<false>, dim3(nA + nB), dim3(256), 0, stream, dT, dT2, Wx0, ldw, emb, dEmb, dWx0,
+                           db0, V, E, G, g_lo, g_hi, nA, etA, etB);
     return arcvae_launch_status();
 }
 
