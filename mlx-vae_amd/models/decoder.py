@@ -7,6 +7,7 @@ B*V (row, token) pairs at once and turn the teacher-forcing / argmax-feedback lo
 walk (arcvae_hip/csrc/decoder.hip)."""
 from __future__ import annotations
 
+import ctypes as C
 from typing import Optional, Sequence, Tuple
 
 import numpy as np
@@ -25,6 +26,15 @@ def draw_coins(T: int, ratio: float, has_target: bool = True) -> np.ndarray:
     if not has_target:
         return np.zeros(T, dtype=np.uint8)
     return np.array([np.random.rand() < ratio for _ in range(T)], dtype=np.uint8)
+
+
+def check_temperature(temperature, finite: bool = False) -> None:
+    """ValueError unless temperature > 0 (NaN refused).  Known and kept as it is: an INFINITE temperature is accepted by
+    generate_beam, sequence_log_prob and the sampling paths, and refused (finite=True) by the chain methods generate_map,
+    generate_kbest, token_marginals and length_distribution, whose kernels refuse it.  Making the two agree changes what a
+    method accepts: a change of its own, not a tidying."""
+    if not (0.0 < float(temperature) < float("inf") if finite else temperature > 0.0):
+        raise ValueError("temperature must be finite and > 0" if finite else "temperature must be > 0")
 
 
 class MLXAutoregressiveDecoder(HipModule):
@@ -62,15 +72,9 @@ class MLXAutoregressiveDecoder(HipModule):
         """logits [B,T,V] (models/decoder.py:113-190).  `coins` (optional) injects the per-step
         teacher-forcing decisions; by default they are drawn from np.random exactly as the reference does."""
         dev = self.store.device
-        cond = as_f32(conditions, dev)
-        B = cond.shape[0]
-        if target_seq is not None:
-            tgt = as_tokens(target_seq, dev)
-            T = tgt.shape[1]
-        else:
-            tgt, T = None, max_length
-        ws = self.workspace(B, T)
-        ws.cond.copy_(cond.reshape(B, self.num_conditions))
+        tgt = None if target_seq is None else as_tokens(target_seq, dev)
+        T = max_length if tgt is None else tgt.shape[1]
+        ws, B = self.load_conditions(conditions, T)
         if tgt is not None:
             ws.x.copy_(tgt)
         else:
@@ -78,7 +82,7 @@ class MLXAutoregressiveDecoder(HipModule):
         if coins is None:
             coins = draw_coins(T, teacher_forcing_ratio, tgt is not None)
         ws.coins.copy_(torch.as_tensor(np.asarray(coins).astype(np.uint8)).to(dev))
-        E.decoder_forward_dense(self.store, ws, self.dims)
+        self.dense_table(ws, forward_only=False)
         E.decoder_chain(ws, self.dims)
         out = torch.empty(B, T, self.vocab_size, dtype=torch.float32, device=dev)
         call("arcvae_dec_gather_logits", ptr(ws.logits), ptr(ws.fed), ptr(out), B, T, self.vocab_size, stream_ptr())
@@ -89,8 +93,7 @@ class MLXAutoregressiveDecoder(HipModule):
         sum over t <= e of log_softmax(logits(fed_t) / temperature)[x_t], fed_0 = 0 (the start token), fed_t = x_{t-1}, e the
         first end_token (T-1 without one).  One dense pass (B*V rows) + arcvae_dec_row_lse + arcvae_dec_sequence_logprob: the
         scores generate_beam returns are this value of the tokens it returns, bit for bit."""
-        if not temperature > 0.0:
-            raise ValueError("temperature must be > 0")
+        check_temperature(temperature)
         dev = self.store.device
         cond = as_f32(conditions, dev)
         tgt = as_tokens(target_seq, dev)
@@ -101,13 +104,40 @@ class MLXAutoregressiveDecoder(HipModule):
             raise ValueError("conditions must be [B, num_conditions]")
         if bool(((tgt < 0) | (tgt >= self.vocab_size)).any()):
             raise ValueError(f"target_seq tokens must lie in [0, {self.vocab_size})")
-        ws = self.workspace(B, T)
-        ws.cond.copy_(cond.reshape(B, self.num_conditions))
-        E.decoder_forward_dense(self.store, ws, self.dims, mode=0, keep_gpre=False, alone=True)
-        lse = torch.empty(B * self.vocab_size, dtype=torch.float32, device=dev)
+        ws, _ = self.load_conditions(cond, T, B)
+        self.dense_table(ws)
+        lse = self.table_lse(ws, temperature)
         out = torch.empty(B, dtype=torch.float32, device=dev)
-        call("arcvae_dec_row_lse", ptr(ws.logits), ptr(lse), B * self.vocab_size, self.vocab_size, float(temperature),
-             stream_ptr())
         call("arcvae_dec_sequence_logprob", ptr(ws.logits), ptr(lse), ptr(tgt), ptr(out), B, T, self.vocab_size,
              self.end_token, float(temperature), stream_ptr())
         return out
+
+    # ---- the one path from conditions to the dense table: every decoder of the table (models/decoder_sampling.py) and
+    # sequence_log_prob go through these.  The copy and the launches stay apart: a captured pass copies outside its graph.
+    def load_conditions(self, conditions, T: int, B: Optional[int] = None):
+        """conditions as f32 on the device, copied into the (B, T) workspace -> (ws, B); B = the conditions' rows unless given."""
+        cond = as_f32(conditions, self.store.device)
+        if B is None:
+            B = cond.shape[0]
+        ws = self.workspace(B, T)
+        ws.cond.copy_(cond.reshape(B, self.num_conditions))
+        return ws, B
+
+    def dense_table(self, ws, mode: int = 0, temperature: float = 1.0, forward_only: bool = True) -> None:
+        """The dense pass over ws.cond: ws.logits [B*V, V] (mode 0), ws.nxt too (mode 1, at `temperature`).  forward_only (every
+        caller but __call__): pre-activations not kept, and no encoder sweep shares the chip."""
+        E.decoder_forward_dense(self.store, ws, self.dims, mode=mode, temperature=temperature, keep_gpre=not forward_only,
+                                alone=forward_only)
+
+    def table_lse(self, ws, temperature: float) -> torch.Tensor:
+        """lse [B*V] float32 of ws.logits / temperature, one per table row (the term every score on the table subtracts)."""
+        rows = ws.B * self.vocab_size
+        lse = torch.empty(rows, dtype=torch.float32, device=self.store.device)
+        call("arcvae_dec_row_lse", ptr(ws.logits), ptr(lse), rows, self.vocab_size, float(temperature), stream_ptr())
+        return lse
+
+    def scratch(self, what: str, *dims) -> torch.Tensor:
+        """uint8 scratch of the size arcvae_dec_`what`_ws_bytes(*dims) asks for."""
+        n = C.c_long(0)
+        call(f"arcvae_dec_{what}_ws_bytes", *dims, C.byref(n))
+        return torch.empty(n.value, dtype=torch.uint8, device=self.store.device)

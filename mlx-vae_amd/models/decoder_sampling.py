@@ -9,16 +9,22 @@ sampling the reference marks TODO (decoder_sampling.py:115-116): an extension wi
 `generate_beam` (beam search with scores, csrc/beam.hip); `decoder.sequence_log_prob` scores given sequences; and
 `sample=True` with `top_k` / `top_p` (truncated sampling, csrc/sample.hip); and `generate_map` / `token_marginals` /
 `length_distribution`: the exact most probable sequence and the exact per-step token and length distributions of the chain the
-dense table defines (csrc/chain.hip); and `generate_kbest`: the exact K most probable sequences of that chain (csrc/kbest.hip)."""
+dense table defines (csrc/chain.hip); and `generate_kbest`: the exact K most probable sequences of that chain (csrc/kbest.hip).
+
+Every method is its argument checks, the decoder's one path to the table -- `load_conditions`, `dense_table`, `table_lse`,
+`scratch` (models/decoder.py) -- and its own kernel.  What the methods share beyond that is written once below: `_state` +
+`_launch` (the per-key buffers in `self._graphs` and the eager / capture / replay protocol of the two captured walks),
+`_check_lengths`, `_check_chain`, `_table`, `_outputs`, and `_cut` / `_stopped` (early stopping).  A further decoder of the
+table is one method of that shape."""
 from __future__ import annotations
+
+import ctypes as C
 
 import torch
 
-from arcvae_hip import engine as E
 from arcvae_hip._lib import call, ptr, stream_ptr
-from arcvae_hip.module import as_f32
 
-from .decoder import MLXAutoregressiveDecoder
+from .decoder import MLXAutoregressiveDecoder, check_temperature
 
 
 class MLXAutoregressiveDecoderSampling:
@@ -56,62 +62,40 @@ class MLXAutoregressiveDecoderSampling:
         if sample:
             return self._generate_categorical(conditions, max_length, temperature, early_stopping, int(seed))
         dec = self.decoder
-        dev = dec.store.device
-        cond = as_f32(conditions, dev)
-        B = cond.shape[0]
-        ws = dec.workspace(B, max_length)
-        ws.cond.copy_(cond.reshape(B, dec.num_conditions))
-        key = (B, max_length, float(temperature))
-        if key not in self._graphs:
-            self._graphs[key] = dict(tokens=torch.zeros(B, max_length, dtype=torch.int32, device=dev),
-                                     first_end=torch.zeros(B, dtype=torch.int32, device=dev), graph=None)
-        st = self._graphs[key]
+        ws, B = dec.load_conditions(conditions, max_length)
+        st = self._state((B, max_length, float(temperature)), B, max_length)
 
         def enqueue():
-            E.decoder_forward_dense(dec.store, ws, dec.dims, mode=1, temperature=temperature, keep_gpre=False, alone=True)
+            dec.dense_table(ws, mode=1, temperature=temperature)
             call("arcvae_dec_sample_chain", ptr(ws.nxt), ptr(st["tokens"]), ptr(st["first_end"]), B, dec.vocab_size,
                  max_length, dec.end_token, stream_ptr())
 
-        if not use_graph:
-            enqueue()
-        elif st["graph"] is None:
-            enqueue()  # first call runs eagerly, then the decode pass is captured for replay
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                enqueue()
-            st["graph"] = g
-        else:
-            st["graph"].replay()
-        tokens = st["tokens"]
-        if early_stopping:
-            # reference: the loop breaks at the first step t where every row has already ended, i.e. after
-            # max_b(first EOS index) + 1 tokens; one host read replaces its per-step mx.all() sync
-            t_stop = int(st["first_end"].max().item()) + 1
-            tokens = tokens[:, :min(t_stop, max_length)]
-        return tokens.clone()
+        _launch(st, enqueue, use_graph)
+        return _stopped(st["tokens"], st["first_end"], early_stopping)
+
+    def _state(self, key, B: int, T: int, more=None) -> dict:
+        """self._graphs[key], made on the key's first use: the walk's output buffers, what else the pass keeps (`more()`) and the
+        captured graph (None until _launch captures it)."""
+        if key not in self._graphs:
+            dev = self.decoder.store.device
+            self._graphs[key] = dict(tokens=torch.zeros(B, T, dtype=torch.int32, device=dev),
+                                     first_end=torch.zeros(B, dtype=torch.int32, device=dev), graph=None,
+                                     **(more() if more else {}))
+        return self._graphs[key]
 
     def _generate_categorical(self, conditions, max_length: int, temperature: float, early_stopping: bool, seed: int) -> torch.Tensor:
         """One dense decoder pass (raw logits of all B*V (row, token) pairs), then arcvae_dec_sample_chain_categorical: a wave per
         row walks start token -> sampled token -> ... through the table of distributions.  Eager launches (the seed is a launch
         argument; the greedy path's captured pass is untouched)."""
-        import ctypes as C
-        if not temperature > 0.0:
-            raise ValueError("temperature must be > 0 for categorical sampling")
+        check_temperature(temperature)
         dec = self.decoder
-        dev = dec.store.device
-        cond = as_f32(conditions, dev)
-        B = cond.shape[0]
-        ws = dec.workspace(B, max_length)
-        ws.cond.copy_(cond.reshape(B, dec.num_conditions))
-        tokens = torch.zeros(B, max_length, dtype=torch.int32, device=dev)
-        first_end = torch.zeros(B, dtype=torch.int32, device=dev)
-        E.decoder_forward_dense(dec.store, ws, dec.dims, mode=0, keep_gpre=False, alone=True)
+        ws, B = dec.load_conditions(conditions, max_length)
+        tokens = torch.zeros(B, max_length, dtype=torch.int32, device=dec.store.device)
+        first_end = torch.zeros(B, dtype=torch.int32, device=dec.store.device)
+        dec.dense_table(ws)
         call("arcvae_dec_sample_chain_categorical", ptr(ws.logits), ptr(tokens), ptr(first_end), B, dec.vocab_size, max_length,
              dec.end_token, float(temperature), C.c_ulonglong(seed & 0xFFFFFFFFFFFFFFFF), stream_ptr())
-        if early_stopping:
-            tokens = tokens[:, :min(int(first_end.max().item()) + 1, max_length)]
-        return tokens.clone()
+        return _stopped(tokens, first_end, early_stopping)
 
     def _generate_topkp(self, conditions, max_length: int, temperature: float, early_stopping: bool, use_graph: bool, seed: int,
                         top_k, top_p) -> torch.Tensor:
@@ -119,9 +103,7 @@ class MLXAutoregressiveDecoderSampling:
         truncates every table row once, and a wave per row walks start token -> drawn token -> ... through those lists.  The seed is
         read by the kernel from a device word written before the launch, so the pass is captured once per (B, max_length,
         temperature, top_k, top_p) and replayed for every seed; use_graph=False launches the same kernels eagerly."""
-        import ctypes as C
-        if not temperature > 0.0:
-            raise ValueError("temperature must be > 0 for top-k / top-p sampling")
+        check_temperature(temperature)
         k = 0 if top_k is None else int(top_k)
         if top_k is not None and k < 1:
             raise ValueError("top_k must be >= 1")
@@ -129,46 +111,52 @@ class MLXAutoregressiveDecoderSampling:
         if not 0.0 < p <= 1.0 or not 0.0 < float(C.c_float(p).value) <= 1.0:
             raise ValueError("top_p must lie in (0, 1]")
         dec = self.decoder
-        if dec.vocab_size > 256:
+        V = dec.vocab_size
+        if V > 256:
             raise ValueError("top-k / top-p sampling needs vocab_size <= 256")
-        dev = dec.store.device
-        cond = as_f32(conditions, dev)
-        B = cond.shape[0]
-        ws = dec.workspace(B, max_length)
-        ws.cond.copy_(cond.reshape(B, dec.num_conditions))
-        key = ("topkp", B, max_length, float(temperature), k, p)
-        if key not in self._graphs:
-            nbytes = C.c_long(0)
-            call("arcvae_dec_topkp_ws_bytes", B, dec.vocab_size, k, C.byref(nbytes))
-            self._graphs[key] = dict(tokens=torch.zeros(B, max_length, dtype=torch.int32, device=dev),
-                                     first_end=torch.zeros(B, dtype=torch.int32, device=dev),
-                                     seed=torch.zeros(1, dtype=torch.int64, device=dev),
-                                     scratch=torch.empty(nbytes.value, dtype=torch.uint8, device=dev), graph=None)
-        st = self._graphs[key]
+        ws, B = dec.load_conditions(conditions, max_length)
+        st = self._state(("topkp", B, max_length, float(temperature), k, p), B, max_length,
+                         lambda: dict(seed=torch.zeros(1, dtype=torch.int64, device=dec.store.device),
+                                      scratch=dec.scratch("topkp", B, V, k)))
         s64 = seed & 0xFFFFFFFFFFFFFFFF
         st["seed"].fill_(s64 - (1 << 64) if s64 >= 1 << 63 else s64)       # the 64-bit word the kernel reads
 
         def enqueue():
-            E.decoder_forward_dense(dec.store, ws, dec.dims, mode=0, keep_gpre=False, alone=True)
+            dec.dense_table(ws)
             call("arcvae_dec_sample_chain_topkp", ptr(ws.logits), ptr(st["tokens"]), ptr(st["first_end"]), ptr(st["scratch"]),
-                 st["scratch"].numel(), B, dec.vocab_size, max_length, dec.end_token, float(temperature), k, p, ptr(st["seed"]),
-                 stream_ptr())
+                 st["scratch"].numel(), B, V, max_length, dec.end_token, float(temperature), k, p, ptr(st["seed"]), stream_ptr())
 
-        if not use_graph:
-            enqueue()
-        elif st["graph"] is None:
-            enqueue()  # first call runs eagerly, then the decode pass is captured for replay
-            torch.cuda.synchronize()
-            g = torch.cuda.CUDAGraph()
-            with torch.cuda.graph(g):
-                enqueue()
-            st["graph"] = g
-        else:
-            st["graph"].replay()
-        tokens = st["tokens"]
-        if early_stopping:
-            tokens = tokens[:, :min(int(st["first_end"].max().item()) + 1, max_length)]
-        return tokens.clone()
+        _launch(st, enqueue, use_graph)
+        return _stopped(st["tokens"], st["first_end"], early_stopping)
+
+    def _check_lengths(self, max_length, min_length):
+        """(max_length, min_length) as ints, checked as generate_beam, generate_map and generate_kbest need them."""
+        T, m = int(max_length), int(min_length)
+        if T < 1 or not 0 <= m <= T:
+            raise ValueError("need max_length >= 1 and 0 <= min_length <= max_length")
+        if not 0 <= self.pad_token <= 255:
+            raise ValueError("needs 0 <= pad_token <= 255")
+        return T, m
+
+    def _check_chain(self, T: int, temperature) -> None:
+        """What the kernels of csrc/chain.hip and csrc/kbest.hip refuse, as ValueErrors before any device work."""
+        check_temperature(temperature, finite=True)
+        if T < 1:
+            raise ValueError("need max_length >= 1")
+        if self.decoder.vocab_size > 256 or not 0 <= self.end_token < self.decoder.vocab_size:
+            raise ValueError("needs vocab_size <= 256 and 0 <= end_token < vocab_size")
+
+    def _table(self, conditions, T: int, temperature: float):
+        """(ws, lse [B*V], B): the dense table of `conditions` in ws.logits (mode 0) and its rows' lse at `temperature`."""
+        ws, B = self.decoder.load_conditions(conditions, T)
+        self.decoder.dense_table(ws)
+        return ws, self.decoder.table_lse(ws, temperature), B
+
+    def _outputs(self, *shape):
+        """(tokens [*lead, T] int32, scores [*lead] float32, lengths [*lead] int32) for shape = (*lead, T), uninitialised."""
+        dev = self.decoder.store.device
+        return (torch.empty(*shape, dtype=torch.int32, device=dev), torch.empty(*shape[:-1], dtype=torch.float32, device=dev),
+                torch.empty(*shape[:-1], dtype=torch.int32, device=dev))
 
     def generate_beam(self, z, conditions, max_length: int = 80, beam_width: int = 4, temperature: float = 1.0,
                       min_length: int = 0, early_stopping: bool = True):
@@ -178,56 +166,19 @@ class MLXAutoregressiveDecoderSampling:
         are broken by parent slot, then token (the lower first).  A slot with no finite candidate (beam_width above what the
         vocabulary can fill) has score -inf and pad tokens.  early_stopping: L = the longest returned hypothesis (first EOS + 1,
         max_length without one); otherwise L = max_length.  Each score equals decoder.sequence_log_prob of its tokens."""
-        import ctypes as C
-        dec = self.decoder
-        V = dec.vocab_size
-        if not temperature > 0.0:
-            raise ValueError("temperature must be > 0")
-        if not 1 <= int(beam_width) <= 32:
+        V, K = self.decoder.vocab_size, int(beam_width)
+        check_temperature(temperature)
+        if not 1 <= K <= 32:
             raise ValueError("beam_width must lie in [1, 32]")
-        if int(max_length) < 1 or not 0 <= int(min_length) <= int(max_length):
-            raise ValueError("need max_length >= 1 and 0 <= min_length <= max_length")
-        if V > 256 or not 0 <= self.pad_token <= 255:
-            raise ValueError("beam search needs vocab_size <= 256 and 0 <= pad_token <= 255")
-        K, T = int(beam_width), int(max_length)
-        dev = dec.store.device
-        cond = as_f32(conditions, dev)
-        B = cond.shape[0]
-        ws = dec.workspace(B, T)
-        ws.cond.copy_(cond.reshape(B, dec.num_conditions))
-        nbytes = C.c_long(0)
-        call("arcvae_dec_beam_ws_bytes", B, K, T, C.byref(nbytes))
-        scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        lse = torch.empty(B * V, dtype=torch.float32, device=dev)
-        tokens = torch.empty(B, K, T, dtype=torch.int32, device=dev)
-        scores = torch.empty(B, K, dtype=torch.float32, device=dev)
-        lengths = torch.empty(B, K, dtype=torch.int32, device=dev)
-        E.decoder_forward_dense(dec.store, ws, dec.dims, mode=0, keep_gpre=False, alone=True)
-        call("arcvae_dec_row_lse", ptr(ws.logits), ptr(lse), B * V, V, float(temperature), stream_ptr())
+        T, min_length = self._check_lengths(max_length, min_length)
+        if V > 256:
+            raise ValueError("beam search needs vocab_size <= 256")
+        ws, lse, B = self._table(conditions, T, temperature)
+        scratch = self.decoder.scratch("beam", B, K, T)
+        tokens, scores, lengths = self._outputs(B, K, T)
         call("arcvae_dec_beam_search", ptr(ws.logits), ptr(lse), ptr(tokens), ptr(scores), ptr(lengths), ptr(scratch),
-             nbytes.value, B, V, K, T, int(min_length), self.end_token, self.pad_token, float(temperature), stream_ptr())
-        if early_stopping:
-            tokens = tokens[:, :, :int(lengths.max().item())].contiguous()
-        return tokens, scores
-
-    def _chain_table(self, conditions, max_length: int, temperature: float):
-        """The dense pass (mode 0) and the rows' lse for `conditions` -> (logits [B*V, V] in the workspace, lse [B*V], B)."""
-        dec = self.decoder
-        if not 0.0 < float(temperature) < float("inf"):
-            raise ValueError("temperature must be finite and > 0")
-        if int(max_length) < 1:
-            raise ValueError("need max_length >= 1")
-        if dec.vocab_size > 256 or not 0 <= self.end_token < dec.vocab_size:
-            raise ValueError("needs vocab_size <= 256 and 0 <= end_token < vocab_size")
-        dev = dec.store.device
-        cond = as_f32(conditions, dev)
-        B = cond.shape[0]
-        ws = dec.workspace(B, int(max_length))
-        ws.cond.copy_(cond.reshape(B, dec.num_conditions))
-        lse = torch.empty(B * dec.vocab_size, dtype=torch.float32, device=dev)
-        E.decoder_forward_dense(dec.store, ws, dec.dims, mode=0, keep_gpre=False, alone=True)
-        call("arcvae_dec_row_lse", ptr(ws.logits), ptr(lse), B * dec.vocab_size, dec.vocab_size, float(temperature), stream_ptr())
-        return ws.logits, lse, B
+             scratch.numel(), B, V, K, T, min_length, self.end_token, self.pad_token, float(temperature), stream_ptr())
+        return (_cut(tokens, lengths).contiguous() if early_stopping else tokens), scores
 
     def generate_map(self, z, conditions, max_length: int = 80, temperature: float = 1.0, min_length: int = 0,
                      early_stopping: bool = True):
@@ -237,25 +188,15 @@ class MLXAutoregressiveDecoderSampling:
         to max_length without one; positions after the end hold pad_token; ties go to the earliest end, then the lowest tokens.
         early_stopping: L = the longest returned sequence; otherwise L = max_length.  Each score equals
         decoder.sequence_log_prob of its tokens bit for bit, and is never below generate_beam's best at any width."""
-        import ctypes as C
-        T = int(max_length)
-        if T < 1 or not 0 <= int(min_length) <= T:
-            raise ValueError("need max_length >= 1 and 0 <= min_length <= max_length")
-        if not 0 <= self.pad_token <= 255:
-            raise ValueError("exact decoding needs 0 <= pad_token <= 255")
-        logits, lse, B = self._chain_table(conditions, T, temperature)
-        V, dev = self.decoder.vocab_size, self.decoder.store.device
-        nbytes = C.c_long(0)
-        call("arcvae_dec_viterbi_ws_bytes", B, V, T, C.byref(nbytes))
-        scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        tokens = torch.empty(B, T, dtype=torch.int32, device=dev)
-        scores = torch.empty(B, dtype=torch.float32, device=dev)
-        lengths = torch.empty(B, dtype=torch.int32, device=dev)
-        call("arcvae_dec_viterbi", ptr(logits), ptr(lse), ptr(tokens), ptr(scores), ptr(lengths), ptr(scratch), nbytes.value, B, V,
-             T, int(min_length), self.end_token, self.pad_token, float(temperature), stream_ptr())
-        if early_stopping:
-            tokens = tokens[:, :int(lengths.max().item())].contiguous()
-        return tokens, scores
+        T, min_length = self._check_lengths(max_length, min_length)
+        self._check_chain(T, temperature)
+        V = self.decoder.vocab_size
+        ws, lse, B = self._table(conditions, T, temperature)
+        scratch = self.decoder.scratch("viterbi", B, V, T)
+        tokens, scores, lengths = self._outputs(B, T)
+        call("arcvae_dec_viterbi", ptr(ws.logits), ptr(lse), ptr(tokens), ptr(scores), ptr(lengths), ptr(scratch), scratch.numel(),
+             B, V, T, min_length, self.end_token, self.pad_token, float(temperature), stream_ptr())
+        return (_cut(tokens, lengths).contiguous() if early_stopping else tokens), scores
 
     def generate_kbest(self, z, conditions, max_length: int = 80, num_best: int = 4, temperature: float = 1.0, min_length: int = 0,
                        early_stopping: bool = True):
@@ -266,37 +207,28 @@ class MLXAutoregressiveDecoderSampling:
         beam_width = num_best.  A slot that no sequence fills (num_best above the number of admissible sequences) has score -inf
         and pad tokens.  early_stopping: L = the longest returned sequence (at least 1); otherwise L = max_length.  Each score
         equals decoder.sequence_log_prob of its tokens bit for bit; exp(scores).sum(1) is the probability mass the list covers."""
-        import ctypes as C
-        K, T = int(num_best), int(max_length)
+        K = int(num_best)
         if not 1 <= K <= 32:
             raise ValueError("num_best must lie in [1, 32]")
-        if T < 1 or not 0 <= int(min_length) <= T:
-            raise ValueError("need max_length >= 1 and 0 <= min_length <= max_length")
-        if not 0 <= self.pad_token <= 255:
-            raise ValueError("exact decoding needs 0 <= pad_token <= 255")
-        logits, lse, B = self._chain_table(conditions, T, temperature)
-        V, dev = self.decoder.vocab_size, self.decoder.store.device
-        nbytes = C.c_long(0)
-        call("arcvae_dec_kbest_ws_bytes", B, V, K, T, C.byref(nbytes))
-        scratch = torch.empty(nbytes.value, dtype=torch.uint8, device=dev)
-        tokens = torch.empty(B, K, T, dtype=torch.int32, device=dev)
-        scores = torch.empty(B, K, dtype=torch.float32, device=dev)
-        lengths = torch.empty(B, K, dtype=torch.int32, device=dev)
-        call("arcvae_dec_kbest", ptr(logits), ptr(lse), ptr(tokens), ptr(scores), ptr(lengths), ptr(scratch), nbytes.value, B, V,
-             K, T, int(min_length), self.end_token, self.pad_token, float(temperature), stream_ptr())
-        if early_stopping:
-            tokens = tokens[:, :, :max(int(lengths.max().item()), 1)].contiguous()
-        return tokens, scores
+        T, min_length = self._check_lengths(max_length, min_length)
+        self._check_chain(T, temperature)
+        V = self.decoder.vocab_size
+        ws, lse, B = self._table(conditions, T, temperature)
+        scratch = self.decoder.scratch("kbest", B, V, K, T)
+        tokens, scores, lengths = self._outputs(B, K, T)
+        call("arcvae_dec_kbest", ptr(ws.logits), ptr(lse), ptr(tokens), ptr(scores), ptr(lengths), ptr(scratch), scratch.numel(),
+             B, V, K, T, min_length, self.end_token, self.pad_token, float(temperature), stream_ptr())
+        return (_cut(tokens, lengths, floor=1).contiguous() if early_stopping else tokens), scores
 
     def token_marginals(self, conditions, max_length: int = 80, temperature: float = 1.0) -> torch.Tensor:
         """Extension (absent in the reference): [B, max_length, V] float32, entry [b, t, v] = P(the token at step t is v and no
         end_token came before t) of what sample=True draws at this temperature -- the chain's forward recursion, exact up to fp32
         rounding (include/arcvae_hip.h arcvae_dec_chain_marginals).  Column end_token is the length distribution."""
-        T = int(max_length)
-        logits, lse, B = self._chain_table(conditions, T, temperature)
-        V = self.decoder.vocab_size
+        T, V = int(max_length), self.decoder.vocab_size
+        self._check_chain(T, temperature)
+        ws, lse, B = self._table(conditions, T, temperature)
         alive = torch.empty(B, T, V, dtype=torch.float32, device=self.decoder.store.device)
-        call("arcvae_dec_chain_marginals", ptr(logits), ptr(lse), ptr(alive), B, V, T, self.end_token, float(temperature),
+        call("arcvae_dec_chain_marginals", ptr(ws.logits), ptr(lse), ptr(alive), B, V, T, self.end_token, float(temperature),
              stream_ptr())
         return alive
 
@@ -307,3 +239,31 @@ class MLXAutoregressiveDecoderSampling:
         last = alive[:, -1, :]
         rest = last.sum(dim=1) - last[:, self.end_token]
         return torch.cat([alive[:, :, self.end_token], rest[:, None]], dim=1)
+
+
+def _launch(st: dict, enqueue, use_graph: bool) -> None:
+    """Run `enqueue` (launches only: what it reads is written before) for the state `st` of one key: eagerly without use_graph;
+    on the key's first use eagerly, then once more under capture; afterwards as a replay, which launches nothing from Python."""
+    if not use_graph:
+        enqueue()
+    elif st["graph"] is None:
+        enqueue()  # first call runs eagerly, then the decode pass is captured for replay
+        torch.cuda.synchronize()
+        g = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(g):
+            enqueue()
+        st["graph"] = g
+    else:
+        st["graph"].replay()
+
+
+def _cut(tokens: torch.Tensor, lengths: torch.Tensor, floor: int = 0, extra: int = 0) -> torch.Tensor:
+    """Early stopping: the leading max(lengths) + extra columns of tokens [..., T], at least `floor` of them (a view; one host
+    read of the device maximum replaces a per-step check)."""
+    return tokens[..., :max(int(lengths.max().item()) + extra, floor)]
+
+
+def _stopped(tokens: torch.Tensor, first_end: torch.Tensor, early_stopping: bool) -> torch.Tensor:
+    """What a walk returns, as a copy of its buffer.  Early stopping as in the reference: its loop breaks at the first step where
+    every row has already ended, i.e. after max_b(first EOS index) + 1 tokens."""
+    return (_cut(tokens, first_end, extra=1) if early_stopping else tokens).clone()

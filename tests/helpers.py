@@ -1,6 +1,8 @@
 """Shared test helpers: oracle <-> engine plumbing and error metrics."""
 from __future__ import annotations
 
+import ctypes as C
+
 import numpy as np
 import torch
 
@@ -67,6 +69,66 @@ def make_case(cfg: O.Config, B: int, T: int, tf_ratio: float = 0.7, seed: int = 
     eps = np.random.RandomState(4321).standard_normal((B, cfg.Z)).astype(np.float32)
     coins = O.draw_coins(np.random.RandomState(seed + 1), T, tf_ratio)
     return params, x, cond, eps, coins
+
+
+def lib():
+    """arcvae_hip._lib, imported on first use (collecting a GPU test file needs no built library)."""
+    from arcvae_hip import _lib
+    return _lib
+
+
+def dev(a, dtype):
+    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
+
+
+def bits(a):
+    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
+
+
+def ws_bytes(name: str, *dims) -> int:
+    """The size query arcvae_dec_`name`_ws_bytes(*dims): the scratch bytes that decoder of the table asks for."""
+    n = C.c_long(0)
+    lib().call(f"arcvae_dec_{name}_ws_bytes", *dims, C.byref(n))
+    return n.value
+
+
+def sampling_vae(cfg: O.Config, params):
+    """ARCVAE holding the oracle parameters `params`, its sampler's own decoder loaded from the trained one."""
+    from models.vae import ARCVAE
+    vae = ARCVAE(vocab_size=cfg.V, embedding_dim=cfg.E, hidden_dim=cfg.H, latent_dim=cfg.Z,
+                 num_conditions=cfg.C, num_layers=cfg.L, dropout=0.2)
+    vae.encoder.load_state_dict(params, prefix="encoder.")
+    vae.decoder.load_state_dict(params, prefix="decoder.")
+    vae.decoder_sampling.load_from_decoder(vae.decoder)
+    return vae
+
+
+def oracle_loglik(params, cfg, cond, tokens, temp, chunk=2048, end=2):
+    """fp64: sum_{t<=e} log_softmax(logits_t / temp)[x_t] from the oracle decoder teacher-forced on every step (all coins
+    true: the token fed at t is x_{t-1}, at t = 0 the start token)."""
+    pd = {k[len("decoder."):]: torch.tensor(v, dtype=torch.float64) for k, v in params.items() if k.startswith("decoder.")}
+    N, T = tokens.shape
+    out = np.zeros(N)
+    for i in range(0, N, chunk):
+        x = torch.tensor(tokens[i:i + chunk], dtype=torch.int64)
+        c = torch.tensor(cond[i:i + chunk], dtype=torch.float64)
+        logits, _ = O.decoder_forward(pd, torch.zeros(x.shape[0], cfg.Z, dtype=torch.float64), c, cfg.L, x, [True] * T)
+        lp = torch.log_softmax(logits / temp, dim=-1).gather(2, x[:, :, None])[:, :, 0].numpy()
+        ended = (tokens[i:i + chunk] == end).cumsum(1)
+        keep = (ended == 0) | ((ended == 1) & (tokens[i:i + chunk] == end))
+        out[i:i + chunk] = (lp * keep).sum(1)
+    return out
+
+
+def ending_model(B: int, end: int = 2):
+    """The model-level case of the exact decoders' tests: TINY with the end token's bias raised (sequences that end, and ones
+    that do not) -> (cfg, params, vae, conditions [B, C], oracle_loglik)."""
+    cfg = TINY
+    params = O.init_params(cfg, 1234)
+    params["decoder.fc_out.bias"][end] += 2.0
+    vae = sampling_vae(cfg, params)
+    cond = np.random.RandomState(3).standard_normal((B, cfg.C)).astype(np.float32)
+    return cfg, params, vae, cond, oracle_loglik
 
 
 def build_engine(cfg: O.Config, params, device="cuda"):

@@ -9,30 +9,19 @@ import torch
 
 import arcvae_oracle as O
 import beam_ref as R
-from helpers import DEFAULT, TINY
+from helpers import DEFAULT, TINY, dev as _dev, lib as _lib, oracle_loglik as _oracle_loglik, sampling_vae as _vae, ws_bytes
 
 pytestmark = pytest.mark.gpu
 END, PAD = 2, 0
 
 
-def _lib():
-    from arcvae_hip import _lib
-    return _lib
-
-
-def _dev(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
 def _search(table, lse, B, V, K, T, min_len, temp):
     L = _lib()
-    n = C.c_long(0)
-    L.call("arcvae_dec_beam_ws_bytes", B, K, T, C.byref(n))
-    ws = torch.empty(n.value, dtype=torch.uint8, device="cuda")
+    ws = torch.empty(ws_bytes("beam", B, K, T), dtype=torch.uint8, device="cuda")
     tok = torch.empty(B, K, T, dtype=torch.int32, device="cuda")
     sc = torch.empty(B, K, dtype=torch.float32, device="cuda")
     ln = torch.empty(B, K, dtype=torch.int32, device="cuda")
-    L.call("arcvae_dec_beam_search", L.ptr(table), L.ptr(lse), L.ptr(tok), L.ptr(sc), L.ptr(ln), L.ptr(ws), n.value, B, V, K, T,
+    L.call("arcvae_dec_beam_search", L.ptr(table), L.ptr(lse), L.ptr(tok), L.ptr(sc), L.ptr(ln), L.ptr(ws), ws.numel(), B, V, K, T,
            min_len, END, PAD, float(temp), L.stream_ptr())
     torch.cuda.synchronize()
     return tok.cpu().numpy(), sc.cpu().numpy(), ln.cpu().numpy()
@@ -95,33 +84,6 @@ def test_row_lse_against_fp64(temp):
         got = out.cpu().numpy().astype(np.float64)
         # relative, with a floor of 1 where lse passes near zero (its absolute error is that of the log of the row sum)
         assert np.all(np.abs(got - ref) <= 1e-6 * np.maximum(1.0, np.abs(ref))), np.abs(got - ref).max()
-
-
-def _vae(cfg, params):
-    from models.vae import ARCVAE
-    vae = ARCVAE(vocab_size=cfg.V, embedding_dim=cfg.E, hidden_dim=cfg.H, latent_dim=cfg.Z,
-                 num_conditions=cfg.C, num_layers=cfg.L, dropout=0.2)
-    vae.encoder.load_state_dict(params, prefix="encoder.")
-    vae.decoder.load_state_dict(params, prefix="decoder.")
-    vae.decoder_sampling.load_from_decoder(vae.decoder)
-    return vae
-
-
-def _oracle_loglik(params, cfg, cond, tokens, temp, chunk=2048):
-    """fp64: sum_{t<=e} log_softmax(logits_t / temp)[x_t] from the oracle decoder teacher-forced on every step (all coins
-    true: the token fed at t is x_{t-1}, at t = 0 the start token)."""
-    pd = {k[len("decoder."):]: torch.tensor(v, dtype=torch.float64) for k, v in params.items() if k.startswith("decoder.")}
-    N, T = tokens.shape
-    out = np.zeros(N)
-    for i in range(0, N, chunk):
-        x = torch.tensor(tokens[i:i + chunk], dtype=torch.int64)
-        c = torch.tensor(cond[i:i + chunk], dtype=torch.float64)
-        logits, _ = O.decoder_forward(pd, torch.zeros(x.shape[0], cfg.Z, dtype=torch.float64), c, cfg.L, x, [True] * T)
-        lp = torch.log_softmax(logits / temp, dim=-1).gather(2, x[:, :, None])[:, :, 0].numpy()
-        ended = (tokens[i:i + chunk] == END).cumsum(1)
-        keep = (ended == 0) | ((ended == 1) & (tokens[i:i + chunk] == END))
-        out[i:i + chunk] = (lp * keep).sum(1)
-    return out
 
 
 @pytest.mark.parametrize("cfg,B,K,T,temp,min_len", [(TINY, 64, 8, 30, 1.0, 2), (TINY, 32, 32, 20, 0.5, 0),

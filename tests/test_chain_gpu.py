@@ -11,32 +11,22 @@ import torch
 import arcvae_oracle as O
 import beam_ref as R
 import chain_ref as X
-from helpers import TINY
+from helpers import dev as _dev, ending_model, lib as _lib, ws_bytes
 
 pytestmark = pytest.mark.gpu
 END, PAD = 2, 0
 U = 2.0 ** -24
 
 
-def _lib():
-    from arcvae_hip import _lib
-    return _lib
-
-
-def _dev(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
 def _viterbi(table_d, lse_d, B, V, T, min_len, temp, pad=PAD):
     L = _lib()
-    n = C.c_long(0)
-    L.call("arcvae_dec_viterbi_ws_bytes", B, V, T, C.byref(n))
-    assert n.value == B * T * V
-    ws = torch.empty(n.value, dtype=torch.uint8, device="cuda")
+    n = ws_bytes("viterbi", B, V, T)
+    assert n == B * T * V
+    ws = torch.empty(n, dtype=torch.uint8, device="cuda")
     tok = torch.full((B, T), -7, dtype=torch.int32, device="cuda")
     sc = torch.empty(B, dtype=torch.float32, device="cuda")
     ln = torch.empty(B, dtype=torch.int32, device="cuda")
-    L.call("arcvae_dec_viterbi", L.ptr(table_d), L.ptr(lse_d), L.ptr(tok), L.ptr(sc), L.ptr(ln), L.ptr(ws), n.value, B, V, T,
+    L.call("arcvae_dec_viterbi", L.ptr(table_d), L.ptr(lse_d), L.ptr(tok), L.ptr(sc), L.ptr(ln), L.ptr(ws), n, B, V, T,
            min_len, END, pad, float(temp), L.stream_ptr())
     torch.cuda.synchronize()
     return tok.cpu().numpy(), sc.cpu().numpy(), ln.cpu().numpy()
@@ -142,13 +132,7 @@ B_M, T_M = 64, 20
 
 @pytest.fixture(scope="module")
 def model():
-    import test_beam_gpu as TB
-    cfg = TINY
-    params = O.init_params(cfg, 1234)
-    params["decoder.fc_out.bias"][END] += 2.0                 # (sequences that end, and ones that do not)
-    vae = TB._vae(cfg, params)
-    cond = np.random.RandomState(3).standard_normal((B_M, cfg.C)).astype(np.float32)
-    return cfg, params, vae, cond, TB._oracle_loglik
+    return ending_model(B_M, END)
 
 
 @pytest.mark.parametrize("temp,min_len", [(1.0, 0), (0.5, 6)])

@@ -8,32 +8,16 @@ import numpy as np
 import pytest
 import torch
 
-import arcvae_oracle as O
 import beam_ref as R
 import kbest_ref as KB
-from helpers import TINY
+from helpers import bits as _bits, dev as _dev, ending_model, lib as _lib, ws_bytes
 
 pytestmark = pytest.mark.gpu
 END, PAD = 2, 0
 
 
-def _lib():
-    from arcvae_hip import _lib
-    return _lib
-
-
-def _dev(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
-def _bits(a):
-    return np.ascontiguousarray(a, dtype=np.float32).view(np.uint32)
-
-
 def _ws_bytes(B, V, K, T):
-    n = C.c_long(0)
-    _lib().call("arcvae_dec_kbest_ws_bytes", B, V, K, T, C.byref(n))
-    return n.value
+    return ws_bytes("kbest", B, V, K, T)
 
 
 def _kbest(table_d, lse_d, B, V, K, T, min_len, temp, pad=PAD):
@@ -227,13 +211,7 @@ B_M, T_M, K_M = 64, 20, 8
 
 @pytest.fixture(scope="module")
 def model():
-    import test_beam_gpu as TB
-    cfg = TINY
-    params = O.init_params(cfg, 1234)
-    params["decoder.fc_out.bias"][END] += 2.0                 # (sequences that end, and ones that do not)
-    vae = TB._vae(cfg, params)
-    cond = np.random.RandomState(3).standard_normal((B_M, cfg.C)).astype(np.float32)
-    return cfg, params, vae, cond, TB._oracle_loglik
+    return ending_model(B_M, END)
 
 
 @pytest.mark.parametrize("temp,min_len", [(1.0, 0), (0.5, 6)])

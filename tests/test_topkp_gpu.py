@@ -9,22 +9,13 @@ import torch
 
 import arcvae_oracle as O
 import topkp_ref as R
-from helpers import DEFAULT, TINY
+from helpers import DEFAULT, TINY, dev as _dev, lib as _lib, ws_bytes
 
 pytestmark = pytest.mark.gpu
 END = 2
 
 
-def _lib():
-    from arcvae_hip import _lib
-    return _lib
-
-
-def _dev(a, dtype):
-    return torch.as_tensor(np.ascontiguousarray(a), dtype=dtype, device="cuda")
-
-
-def _vae(cfg, params):
+def _vae(cfg, params):          # (not helpers.sampling_vae: the sampler's own decoder loaded directly, the rest left as drawn)
     from models.vae import ARCVAE
     vae = ARCVAE(vocab_size=cfg.V, embedding_dim=cfg.E, hidden_dim=cfg.H, latent_dim=cfg.Z, num_conditions=cfg.C,
                  num_layers=cfg.L)
@@ -47,9 +38,7 @@ def _rows(table_d, V, temp, k, p, rows=None):
 
 
 def _ws(B, V, k):
-    n = C.c_long(0)
-    _lib().call("arcvae_dec_topkp_ws_bytes", B, V, int(k), C.byref(n))
-    return torch.empty(n.value, dtype=torch.uint8, device="cuda")
+    return torch.empty(ws_bytes("topkp", B, V, int(k)), dtype=torch.uint8, device="cuda")
 
 
 def _walk(table_d, B, V, T, temp, k, p, seed):

@@ -10,7 +10,6 @@ Also reported: the share of the 10 000 rows whose MAP score is strictly above th
 below), and a kernel-level split of one bs-1024 batch from device events around each launch (median of --reps).  Prints one
 JSON line (and writes it to --out when given)."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -21,7 +20,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mlx-vae_amd"))
 import torch  # noqa: E402
-from arcvae_hip import engine as E  # noqa: E402
 from arcvae_hip._lib import call, ptr, stream_ptr  # noqa: E402
 from models.vae import ARCVAE  # noqa: E402
 
@@ -56,22 +54,19 @@ def med(v):
 def kernel_split(T):
     """Device time of each launch of one bs-1024 batch: the dense pass, the lse, the Viterbi and the marginals kernels."""
     dec, cond = samp.decoder, conds[0]
-    B, V = cond.shape[0], samp.decoder.vocab_size
-    ws = dec.workspace(B, T)
-    ws.cond.copy_(cond.reshape(B, dec.num_conditions))
-    lse = torch.empty(B * V, dtype=torch.float32, device="cuda")
-    n = C.c_long(0)
-    call("arcvae_dec_viterbi_ws_bytes", B, V, T, C.byref(n))
-    scratch = torch.empty(n.value, dtype=torch.uint8, device="cuda")
+    V = dec.vocab_size
+    ws, B = dec.load_conditions(cond, T)
+    lse = torch.empty(B * V, dtype=torch.float32, device="cuda")         # (row_lse is timed as a bare launch into this buffer)
+    scratch = dec.scratch("viterbi", B, V, T)
     tok = torch.empty(B, T, dtype=torch.int32, device="cuda")
     sc = torch.empty(B, dtype=torch.float32, device="cuda")
     ln = torch.empty(B, dtype=torch.int32, device="cuda")
     alive = torch.empty(B, T, V, dtype=torch.float32, device="cuda")
     steps = {
-        "dense_pass": lambda: E.decoder_forward_dense(dec.store, ws, dec.dims, mode=0, keep_gpre=False, alone=True),
+        "dense_pass": lambda: dec.dense_table(ws),
         "row_lse": lambda: call("arcvae_dec_row_lse", ptr(ws.logits), ptr(lse), B * V, V, 1.0, stream_ptr()),
-        "viterbi": lambda: call("arcvae_dec_viterbi", ptr(ws.logits), ptr(lse), ptr(tok), ptr(sc), ptr(ln), ptr(scratch), n.value,
-                                B, V, T, 0, samp.end_token, samp.pad_token, 1.0, stream_ptr()),
+        "viterbi": lambda: call("arcvae_dec_viterbi", ptr(ws.logits), ptr(lse), ptr(tok), ptr(sc), ptr(ln), ptr(scratch),
+                                scratch.numel(), B, V, T, 0, samp.end_token, samp.pad_token, 1.0, stream_ptr()),
         "chain_marginals": lambda: call("arcvae_dec_chain_marginals", ptr(ws.logits), ptr(lse), ptr(alive), B, V, T,
                                         samp.end_token, 1.0, stream_ptr()),
     }

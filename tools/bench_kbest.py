@@ -9,7 +9,6 @@ strictly above the beam's at the same K (none is ever below: asserted), the mean
 covers, and the kernel alone on one bs-1024 batch from device events around single launches (median of --reps).  Prints one JSON
 line (and writes it to --out when given)."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -20,7 +19,6 @@ import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 sys.path.insert(0, os.path.join(ROOT, "mlx-vae_amd"))
 import torch  # noqa: E402
-from arcvae_hip import engine as E  # noqa: E402
 from arcvae_hip._lib import call, ptr, stream_ptr  # noqa: E402
 from models.vae import ARCVAE  # noqa: E402
 
@@ -55,17 +53,13 @@ def med(v):
 def kernel_alone(T):
     """Device time of arcvae_dec_kbest alone on one bs-1024 batch, per K (the dense pass and the lse are made once before)."""
     dec, cond = samp.decoder, conds[0]
-    B, V = cond.shape[0], dec.vocab_size
-    ws = dec.workspace(B, T)
-    ws.cond.copy_(cond.reshape(B, dec.num_conditions))
-    lse = torch.empty(B * V, dtype=torch.float32, device="cuda")
-    E.decoder_forward_dense(dec.store, ws, dec.dims, mode=0, keep_gpre=False, alone=True)
-    call("arcvae_dec_row_lse", ptr(ws.logits), ptr(lse), B * V, V, 1.0, stream_ptr())
+    V = dec.vocab_size
+    ws, B = dec.load_conditions(cond, T)
+    dec.dense_table(ws)
+    lse = dec.table_lse(ws, 1.0)
     out = {}
     for K in widths:
-        n = C.c_long(0)
-        call("arcvae_dec_kbest_ws_bytes", B, V, K, T, C.byref(n))
-        scratch = torch.empty(n.value, dtype=torch.uint8, device="cuda")
+        scratch = dec.scratch("kbest", B, V, K, T)
         tok = torch.empty(B, K, T, dtype=torch.int32, device="cuda")
         sc = torch.empty(B, K, dtype=torch.float32, device="cuda")
         ln = torch.empty(B, K, dtype=torch.int32, device="cuda")
@@ -74,12 +68,12 @@ def kernel_alone(T):
             a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
             torch.cuda.synchronize()
             a.record()
-            call("arcvae_dec_kbest", ptr(ws.logits), ptr(lse), ptr(tok), ptr(sc), ptr(ln), ptr(scratch), n.value, B, V, K, T, 0,
-                 samp.end_token, samp.pad_token, 1.0, stream_ptr())
+            call("arcvae_dec_kbest", ptr(ws.logits), ptr(lse), ptr(tok), ptr(sc), ptr(ln), ptr(scratch), scratch.numel(), B, V, K, T,
+                 0, samp.end_token, samp.pad_token, 1.0, stream_ptr())
             b.record()
             torch.cuda.synchronize()
             ts.append(a.elapsed_time(b))
-        out[str(K)] = {"kbest_kernel_ms": round(med(ts[1:]), 4), "scratch_mb": round(n.value / 2 ** 20, 1)}
+        out[str(K)] = {"kbest_kernel_ms": round(med(ts[1:]), 4), "scratch_mb": round(scratch.numel() / 2 ** 20, 1)}
     return out
 
 

@@ -8,7 +8,6 @@ device word before the replay, plus the host read of first_end for early stoppin
 table: one arcvae_dec_sample_chain_topkp call (pre-pass over all B * V rows + walk) and the inspection kernel over the same rows.
 Prints one JSON line (and writes it to --out when given).  Per-kernel times: a separate profiler run with --reps 1."""
 import argparse
-import ctypes as C
 import json
 import os
 import sys
@@ -97,15 +96,13 @@ for T in [int(t) for t in args.max_lengths.split(",")]:
     rcum = torch.empty(B * V, V, dtype=torch.float32, device="cuda")
     pl = {}
     for name, k, p in (("top_k_20", 20, 1.0), ("top_p_0.9", 0, 0.9), ("top_k_20_top_p_0.9", 20, 0.9)):
-        nb = C.c_long(0)
-        call("arcvae_dec_topkp_ws_bytes", B, V, k, C.byref(nb))
-        ws = torch.empty(nb.value, dtype=torch.uint8, device="cuda")
-        chain = events(lambda: call("arcvae_dec_sample_chain_topkp", ptr(table), ptr(tok), ptr(fe), ptr(ws), nb.value, B, V, T, 2, 1.0,
-                                    k, p, ptr(seed), stream_ptr()))
+        ws = samp.decoder.scratch("topkp", B, V, k)
+        chain = events(lambda: call("arcvae_dec_sample_chain_topkp", ptr(table), ptr(tok), ptr(fe), ptr(ws), ws.numel(), B, V, T, 2,
+                                    1.0, k, p, ptr(seed), stream_ptr()))
         rows = events(lambda: call("arcvae_dec_topkp_rows", ptr(table), B * V, None, B * V, V, 1.0, k, p, ptr(cnt), ptr(rtok),
                                    ptr(rcum), stream_ptr()))
         pl[name] = {"prepass_plus_walk_ms_per_batch": round(chain, 4), "inspect_all_rows_ms_per_batch": round(rows, 4),
-                    "workspace_MB": round(nb.value / 1e6, 2)}
+                    "workspace_MB": round(ws.numel() / 1e6, 2)}
     res["kernels"][f"max_length={T}"] = pl
 line = json.dumps(res)
 print(line)
