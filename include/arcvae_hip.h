@@ -441,6 +441,51 @@ int arcvae_dec_kbest_ws_bytes(int B, int V, int K, int max_len, long* bytes);
 int arcvae_dec_kbest(const float* dense_logits, const float* lse, int32_t* tokens /*[B,K,max_len]*/, float* scores /*[B,K]*/,
                      int32_t* lengths /*[B,K]*/, void* ws, long ws_bytes, int B, int V, int K, int max_len, int min_len,
                      int end_token, int pad_token, float temperature, arcvae_stream_t stream);
+/* EXTENSION (no reference counterpart) -- length-normalised exact decoding and the best sequence of every length, on the same chain.
+ * The step term lp, the raw score s <- fl(s + lp), the start token 0, the admissible sequences, min_len, pad_token and the limits
+ * are those of arcvae_dec_viterbi / arcvae_dec_kbest; anything else is ARCVAE_ERR_ARG before any launch; no host state,
+ * asynchronous on `stream`, capture-safe.  The workspace queries arcvae_dec_viterbi_ws_bytes / arcvae_dec_kbest_ws_bytes serve.
+ * len_div: a DEVICE array of max_len fp32 divisors, entry n-1 for the sequences of length n (the end token counts; a sequence
+ *   without one has n = max_len); NULL = all ones.  Entries must be finite and > 0; the kernels cannot refuse a device array, so
+ *   the caller checks (models/decoder_sampling.py does); a violating array is outside the contract, and the kernels still write
+ *   only tokens in [0, V) or pad_token.  A candidate's KEY is fl(raw / d_n): one correctly rounded IEEE fp32 division, never a
+ *   reciprocal and a product.
+ * Exactness: for a fixed n, x -> fl(x / d_n) is non-decreasing, so the best key among the sequences of length n is the key of
+ *   the best raw score of that length -- the e_t the Viterbi recursion forms at step t = n-1 -- and the K best keys of a length
+ *   are the keys of its K best raw scores.  The optimum over all lengths is a maximum over the max_len per-length winners.
+ * arcvae_dec_viterbi_norm.  Recursion and back pointers as arcvae_dec_viterbi.  Candidates, in this order: the end candidates of
+ *   the steps t = min_len .. max_len-1 with key fl(e_t / d[t]); then ONE open candidate, the maximum raw a_{max_len-1}[v] over
+ *   v != end_token, the lowest v on a tie, with key fl(. / d[max_len-1]).  The first candidate is taken; a later one replaces it
+ *   only when its key is strictly greater: the earliest end wins a tie.  (The open candidate is chosen on raw scores so that
+ *   K = 1 of the list form below is this.)  Outputs: tokens [B, max_len], length [B]; score [B] = the key; raw_score [B] =
+ *   bitwise what arcvae_dec_sequence_logprob returns for the tokens; by_length [B, max_len] (NULL allowed) = the raw e_t of EVERY
+ *   step t, whatever min_len is: the best score of any sequence whose first end_token is at position t (length t+1), -inf
+ *   where there is none; open_score [B] (NULL allowed) = the open candidate's raw score, -inf for V = 1.  With len_div all ones
+ *   or NULL, tokens, length and score are bitwise arcvae_dec_viterbi's.
+ * arcvae_dec_viterbi_trace.  Reads the back pointers an arcvae_dec_viterbi / _norm call with the same B, V, max_len left in `ws`
+ *   (same ws_bytes check) and lengths [B] (device).  tokens [B, max_len] = the sequence that ends with end_token at position
+ *   n_b - 1, followed back through the pointers, then pad_token; its raw score is by_length[b, n_b - 1].  n_b is CLAMPED into
+ *   [0, max_len]; n_b = 0 writes pad tokens only.  One forward call serves any number of traces.
+ * arcvae_dec_kbest_norm.  The lists a_t[v] and their back pointers as arcvae_dec_kbest, on raw scores.  Arriving lists, in this
+ *   order: for t = min_len .. max_len-1 the list into end_token at step t, by rank; then the final list: the first K of the
+ *   stable sort by raw score descending of a_{max_len-1}[v], v != end_token ascending, by rank.  An entry's key is
+ *   fl(raw / d_n); keys within a list stay non-increasing.  Each list is merged stably into the running K-entry result BY KEY,
+ *   the result's entries first on ties.  Outputs: scores [B, K] = the keys, descending; raw_scores [B, K]; tokens, lengths and
+ *   empty slots (by raw score -inf: key and raw -inf, length 0, pad tokens) as arcvae_dec_kbest.
+ *   Properties: scores[b, :] IS the multiset of the K largest keys over all admissible sequences (per length by the
+ *   monotonicity above, across lengths by the merge); the K sequences are pairwise distinct; each raw_scores entry is what
+ *   arcvae_dec_sequence_logprob returns for its tokens, bit for bit; K = 1 equals arcvae_dec_viterbi_norm; all-ones (or NULL)
+ *   divisors equal arcvae_dec_kbest bitwise. */
+int arcvae_dec_viterbi_norm(const float* dense_logits, const float* lse, const float* len_div /*[max_len] or NULL*/,
+                            int32_t* tokens, float* score, float* raw_score, int32_t* length, float* by_length /*or NULL*/,
+                            float* open_score /*or NULL*/, void* ws, long ws_bytes, int B, int V, int max_len, int min_len,
+                            int end_token, int pad_token, float temperature, arcvae_stream_t stream);
+int arcvae_dec_viterbi_trace(const void* ws, long ws_bytes, const int32_t* lengths /*[B]*/, int32_t* tokens /*[B,max_len]*/, int B,
+                             int V, int max_len, int end_token, int pad_token, arcvae_stream_t stream);
+int arcvae_dec_kbest_norm(const float* dense_logits, const float* lse, const float* len_div /*[max_len] or NULL*/,
+                          int32_t* tokens /*[B,K,max_len]*/, float* scores /*[B,K]*/, float* raw_scores /*[B,K]*/,
+                          int32_t* lengths /*[B,K]*/, void* ws, long ws_bytes, int B, int V, int K, int max_len, int min_len,
+                          int end_token, int pad_token, float temperature, arcvae_stream_t stream);
 /* EXTENSION (no reference counterpart: the reference decodes greedily) -- top-k / nucleus (top-p) truncated sampling over the dense
  * logits [B*V, V] of arcvae_dec_forward_dense (mode 0); row r = b*V + c holds batch row b's logits after token c.
  * 1 <= vocab_size <= 256, temperature > 0, top_k >= 0 (0 = all V), 0 < top_p <= 1; anything else (NaN included) is ARCVAE_ERR_ARG.

@@ -96,6 +96,9 @@ SIGNATURES = {
     "arcvae_dec_chain_marginals": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     "arcvae_dec_kbest_ws_bytes": [_i, _i, _i, _i, _lp],
     "arcvae_dec_kbest": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "arcvae_dec_viterbi_norm": [_vp] * 10 + [_l, _i, _i, _i, _i, _i, _i, _f, _vp],
+    "arcvae_dec_viterbi_trace": [_vp, _l, _vp, _vp, _i, _i, _i, _i, _i, _vp],
+    "arcvae_dec_kbest_norm": [_vp] * 8 + [_l, _i, _i, _i, _i, _i, _i, _i, _f, _vp],
     "arcvae_dec_topkp_rows": [_vp, _l, _vp, _l, _i, _f, _i, _f, _vp, _vp, _vp, _vp],
     "arcvae_dec_topkp_ws_bytes": [_i, _i, _i, _lp],
     "arcvae_dec_sample_chain_topkp": [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _f, _i, _f, _vp, _vp],

@@ -18,6 +18,10 @@
 //   viterbi    back pointers go to the caller's scratch as bytes [B, max_len, V]; the back-trace stages them through LDS in
 //              chunks of CHAIN_TRACE_BYTES and one thread follows them.
 //   marginals  writes alive[b, t, :] every step.
+//   viterbi_norm   the same kernel with a pack of extra arguments (ChainNorm): the end column's owner divides e_t by the length's
+//              divisor and compares keys, and stores e_t to the profile where asked; the plain instantiation has an empty pack
+//              and none of that code.
+//   viterbi_trace  a kernel of its own, one workgroup per row: the back-trace alone, from the end token at a given length.
 #include "common.h"
 
 namespace {
@@ -103,12 +107,44 @@ __device__ __forceinline__ ChainQuad chain_quad(const float* cur, const float* t
 }
 
 // ---- Viterbi -----------------------------------------------------------------------------------------------------------------
-template <bool STAGED>
+// back-trace: x_{t-1} = bp[t][x_t] for t = n-1 .. 1 from x_{n-1} = tok, the rows [c0, top) of a chunk staged in LDS; whole
+// workgroup, n uniform; thread 0 follows the pointers (clamped: a row outside the contract stays inside [0, V)).
+__device__ __forceinline__ void chain_backtrace(uint8_t* stage, const uint8_t* bpb, int32_t* out, int n, int tok, int V) {
+    const int tid = threadIdx.x;
+    const int rows = CHAIN_TRACE_BYTES / V;
+    for (int top = n; top > 1; top -= rows) {
+        const int c0 = max(1, top - rows), nb = (top - c0) * V;
+        for (int i = tid; i < nb; i += CHAIN_THREADS) stage[i] = bpb[(long)c0 * V + i];
+        __syncthreads();
+        if (tid == 0) {
+            for (int t = top - 1; t >= c0; --t) {
+                tok = min((int)stage[(t - c0) * V + tok], V - 1);
+                out[t - 1] = tok;
+            }
+        }
+        __syncthreads();
+    }
+}
+
+// What the length-normalised selection adds to the kernel's arguments: the divisors (NULL = all ones) and its further outputs.
+struct ChainNorm {
+    const float* len_div;      // [max_len], entry n-1 divides the raw score of a sequence of length n
+    float* raw_score;          // [B]
+    float* by_length;          // [B, max_len] or NULL: e_t of every step
+    float* open_score;         // [B] or NULL: the open candidate's raw score
+};
+__device__ __forceinline__ ChainNorm chain_norm(ChainNorm a) { return a; }
+__device__ __forceinline__ ChainNorm chain_norm() { return ChainNorm{nullptr, nullptr, nullptr, nullptr}; }
+
+// NormArgs: empty (arcvae_dec_viterbi) or one ChainNorm (arcvae_dec_viterbi_norm).
+template <bool STAGED, class... NormArgs>
 __global__ __launch_bounds__(CHAIN_THREADS) void chain_viterbi_kernel(const float* __restrict__ logits,
                                                                       const float* __restrict__ lse, uint8_t* bp, int32_t* tokens,
                                                                       float* score, int32_t* length, int V, int S, int P,
                                                                       int max_len, int min_len, int end_token, int pad_token,
-                                                                      float inv_temp) {
+                                                                      float inv_temp, NormArgs... norm_args) {
+    constexpr bool NORM = sizeof...(NormArgs) > 0;
+    const ChainNorm na = chain_norm(norm_args...);
     extern __shared__ __align__(16) float smem[];
     float* cur = smem;
     float* nxt = smem + CHAIN_OFF_B;
@@ -131,13 +167,17 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_viterbi_kernel(const floa
     nxt[tid] = -INFINITY;
     __syncthreads();
     // the best end candidate so far, kept by the end token's owner: e_t of the earliest t that attains the maximum
-    float res = 0.f;
+    // (NORM: res is the KEY fl(e_t / d[t]) and raw the e_t it came from)
+    float res = 0.f, raw = 0.f;
     int res_t = 0;
     bool have = false;
     if (owner) {
         const float s = 0.f + chain_term<STAGED, false>(tab, x, ls, 0, v, V, inv_temp);
         if (v == end_token) {
-            if (min_len == 0) { res = s; have = true; }
+            if (NORM) {
+                if (na.by_length) na.by_length[(long)b * max_len] = s;
+                if (min_len == 0) { res = s / (na.len_div ? na.len_div[0] : 1.0f); raw = s; have = true; }
+            } else if (min_len == 0) { res = s; have = true; }
         } else {
             cur[v] = s;
         }
@@ -146,6 +186,8 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_viterbi_kernel(const floa
     for (int t = 1; t < max_len; ++t) {
         float best = -INFINITY;
         int arg = min(lo, V - 1);
+        float div = 1.0f;                                         // (NORM) asked for before the scan, used after it
+        if (NORM && owner && v == end_token && na.len_div) div = na.len_div[t];
         if (active) {
             for (int u = lo; u < hi; u += 4) {
                 const ChainQuad c = chain_quad<STAGED, false>(cur, tab, x, ls, u, v, V, inv_temp);
@@ -166,7 +208,11 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_viterbi_kernel(const floa
             }
             bpb[(long)t * V + v] = (uint8_t)arg;
             if (v == end_token) {
-                if (t >= min_len && (!have || best > res)) { res = best; res_t = t; have = true; }
+                if (NORM) {
+                    if (na.by_length) na.by_length[(long)b * max_len + t] = best;
+                    const float key = best / div;                 // one IEEE division
+                    if (t >= min_len && (!have || key > res)) { res = key; raw = best; res_t = t; have = true; }
+                } else if (t >= min_len && (!have || best > res)) { res = best; res_t = t; have = true; }
             } else {
                 nxt[v] = best;
             }
@@ -182,16 +228,33 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_viterbi_kernel(const floa
         ctl[0] = have;
         ctl[1] = res_t;
         ((float*)ctl)[2] = res;
+        if (NORM) smem[CHAIN_OFF_PV] = raw;                      // (the partial results are dead)
     }
     __syncthreads();
     if (tid == 0) {
         bool chosen = ctl[0] != 0;
         float bs = chosen ? ((float*)ctl)[2] : -INFINITY;
         int n = chosen ? ctl[1] + 1 : max_len, last = chosen ? end_token : 0;
-        for (int w = 0; w < V; ++w) {
-            if (w == end_token) continue;
-            const float s = cur[w];
-            if (!chosen || s > bs) { bs = s; n = max_len; last = w; chosen = true; }
+        if (NORM) {
+            // ONE open candidate: the maximum raw a_{max_len-1}[v], v != end_token, the lowest v of a tie; compared by key
+            float braw = chosen ? smem[CHAIN_OFF_PV] : -INFINITY, os = -INFINITY;
+            int ow = 0;
+            bool any = false;
+            for (int w = 0; w < V; ++w) {
+                if (w == end_token) continue;
+                const float s = cur[w];
+                if (!any || s > os) { os = s; ow = w; any = true; }
+            }
+            const float ok = os / (na.len_div ? na.len_div[max_len - 1] : 1.0f);
+            if (!chosen || ok > bs) { bs = ok; braw = os; n = max_len; last = ow; }
+            na.raw_score[b] = braw;
+            if (na.open_score) na.open_score[b] = os;
+        } else {
+            for (int w = 0; w < V; ++w) {
+                if (w == end_token) continue;
+                const float s = cur[w];
+                if (!chosen || s > bs) { bs = s; n = max_len; last = w; chosen = true; }
+            }
         }
         score[b] = bs;
         length[b] = n;
@@ -202,21 +265,21 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_viterbi_kernel(const floa
     __syncthreads();
     const int n = ctl[1];
     for (int t = n + tid; t < max_len; t += CHAIN_THREADS) out[t] = pad_token;
-    // back-trace: x_{t-1} = bp[t][x_t] for t = n-1 .. 1, the rows [c0, top) of a chunk staged in LDS (the table is dead)
-    const int rows = CHAIN_TRACE_BYTES / V;
-    int tok = ctl[3];
-    for (int top = n; top > 1; top -= rows) {
-        const int c0 = max(1, top - rows), nb = (top - c0) * V;
-        for (int i = tid; i < nb; i += CHAIN_THREADS) stage[i] = bpb[(long)c0 * V + i];
-        __syncthreads();
-        if (tid == 0) {
-            for (int t = top - 1; t >= c0; --t) {
-                tok = min((int)stage[(t - c0) * V + tok], V - 1);
-                out[t - 1] = tok;
-            }
-        }
-        __syncthreads();
-    }
+    chain_backtrace(stage, bpb, out, n, ctl[3], V);          // (the table is dead)
+}
+
+// The sequence that ends with end_token at position n-1 (n = lengths[b] clamped into [0, max_len]), followed back through the
+// pointers a Viterbi launch left in bp; pad_token after it.  One workgroup per row; LDS: one chunk of the back-trace.
+__global__ __launch_bounds__(CHAIN_THREADS) void chain_trace_kernel(const uint8_t* __restrict__ bp,
+                                                                    const int32_t* __restrict__ lengths, int32_t* tokens, int V,
+                                                                    int max_len, int end_token, int pad_token) {
+    extern __shared__ __align__(16) float smem[];
+    const int tid = threadIdx.x, b = blockIdx.x;
+    int32_t* out = tokens + (long)b * max_len;
+    const int n = min(max(lengths[b], 0), max_len);
+    for (int t = n + tid; t < max_len; t += CHAIN_THREADS) out[t] = pad_token;
+    if (n > 0 && tid == 0) out[n - 1] = end_token;
+    chain_backtrace((uint8_t*)smem, bp + (long)b * max_len * V, out, n, end_token, V);
 }
 
 // ---- forward recursion -------------------------------------------------------------------------------------------------------
@@ -301,6 +364,37 @@ extern "C" int arcvae_dec_viterbi(const float* dense_logits, const float* lse, i
     else
         hipLaunchKernelGGL(chain_viterbi_kernel<false>, dim3(B), dim3(CHAIN_THREADS), pl.lds, stream, dense_logits, lse,
                            (uint8_t*)ws, tokens, score, length, V, pl.S, pl.P, max_len, min_len, end_token, pad_token, inv_temp);
+    return arcvae_launch_status();
+}
+
+extern "C" int arcvae_dec_viterbi_norm(const float* dense_logits, const float* lse, const float* len_div, int32_t* tokens,
+                                       float* score, float* raw_score, int32_t* length, float* by_length, float* open_score,
+                                       void* ws, long ws_bytes, int B, int V, int max_len, int min_len, int end_token,
+                                       int pad_token, float temperature, hipStream_t stream) {
+    if (!chain_args_ok(dense_logits, lse, B, V, max_len, end_token, temperature)) return ARCVAE_ERR_ARG;
+    if (!tokens || !score || !raw_score || !length || !ws || min_len < 0 || min_len > max_len || pad_token < 0 || pad_token > 255)
+        return ARCVAE_ERR_ARG;
+    if (ws_bytes < (long)B * max_len * V) return ARCVAE_ERR_ARG;
+    const ChainPlan pl = chain_plan(V, true);
+    const float inv_temp = 1.0f / temperature;
+    const ChainNorm na = {len_div, raw_score, by_length, open_score};
+    if (pl.staged)
+        hipLaunchKernelGGL((chain_viterbi_kernel<true, ChainNorm>), dim3(B), dim3(CHAIN_THREADS), pl.lds, stream, dense_logits, lse,
+                           (uint8_t*)ws, tokens, score, length, V, pl.S, pl.P, max_len, min_len, end_token, pad_token, inv_temp, na);
+    else
+        hipLaunchKernelGGL((chain_viterbi_kernel<false, ChainNorm>), dim3(B), dim3(CHAIN_THREADS), pl.lds, stream, dense_logits, lse,
+                           (uint8_t*)ws, tokens, score, length, V, pl.S, pl.P, max_len, min_len, end_token, pad_token, inv_temp, na);
+    return arcvae_launch_status();
+}
+
+extern "C" int arcvae_dec_viterbi_trace(const void* ws, long ws_bytes, const int32_t* lengths, int32_t* tokens, int B, int V,
+                                        int max_len, int end_token, int pad_token, hipStream_t stream) {
+    if (!ws || !lengths || !tokens || B <= 0 || V < 1 || V > CHAIN_MAX_V || max_len < 1 || end_token < 0 || end_token >= V ||
+        pad_token < 0 || pad_token > 255)
+        return ARCVAE_ERR_ARG;
+    if (ws_bytes < (long)B * max_len * V) return ARCVAE_ERR_ARG;
+    hipLaunchKernelGGL(chain_trace_kernel, dim3(B), dim3(CHAIN_THREADS), CHAIN_TRACE_BYTES, stream, (const uint8_t*)ws, lengths,
+                       tokens, V, max_len, end_token, pad_token);
     return arcvae_launch_status();
 }
 

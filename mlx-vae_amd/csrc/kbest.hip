@@ -21,6 +21,10 @@
 // result.  Both are stable merges with the earlier arrival first, which is the contract's stable sort of all arrivals.  The
 // back-trace is one thread per returned sequence; every pointer is clamped when followed, so a row outside the contract stays
 // inside [0, V).
+// The length-normalised form (arcvae_dec_kbest_norm) is the same kernel with a pack of one extra argument (KbestNorm): the lanes
+// that hold an arriving list divide it by its length's divisor, the running result is ordered by those keys and carries each
+// entry's raw score along; lists, rounds and back pointers stay on raw scores.  The plain instantiations have an empty pack and
+// none of that code.
 #include "common.h"
 
 namespace {
@@ -34,6 +38,9 @@ constexpr int KB_STAGE_LDS = 64 * 1024;      // the step terms are staged when e
 // LDS (dwords): lse [256] | result score, step, (token << 8 | rank): [2][32] each | arriving list: score, (token << 8 | rank): [32]
 // each | list A [K][V4] | list B [K][V4] | step terms [V][V4] when staged
 constexpr int KB_OFF_RES_S = 256, KB_OFF_RES_T = 320, KB_OFF_RES_VR = 384, KB_OFF_ARR_S = 448, KB_OFF_ARR_VR = 480, KB_OFF_LIST = 512;
+// The length-normalised form (arcvae_dec_kbest_norm) orders the result by KEY = fl(raw / d_n): there "score" above is the key, and
+// the raw scores lie beside it: result raw [2][32] | arriving raw [32], before the lists.
+constexpr int KB_OFF_RES_R = 512, KB_OFF_ARR_R = 576, KB_OFF_LIST_NORM = 608;
 
 struct KbestPlan {
     int GL, J;         // lanes per column, heads per lane: (J - 1) * GL < V <= J * GL
@@ -41,12 +48,12 @@ struct KbestPlan {
     unsigned lds;      // dynamic LDS bytes
 };
 
-KbestPlan kbest_plan(int V, int K) {
+KbestPlan kbest_plan(int V, int K, bool norm) {
     KbestPlan p;
     const int V4 = (V + 3) & ~3;
     p.GL = V <= KB_SMALL_V ? 16 : 64;
     p.J = ceil_div(V, p.GL);
-    const unsigned base = (unsigned)(KB_OFF_LIST + 2 * K * V4) * 4u, tab = (unsigned)(V * V4) * 4u;
+    const unsigned base = (unsigned)((norm ? KB_OFF_LIST_NORM : KB_OFF_LIST) + 2 * K * V4) * 4u, tab = (unsigned)(V * V4) * 4u;
     p.staged = base + tab <= (unsigned)KB_STAGE_LDS;           // (never above V 124; always up to V 96)
     p.lds = base + (p.staged ? tab : 0u);
     return p;
@@ -187,9 +194,12 @@ __device__ __forceinline__ void kb_merge(const float* prev, bool active, int V, 
 
 // Stable merge of the running result (K entries, sorted) with an arriving sorted list, the result's entries first on ties, into
 // the other result buffer: an entry's new position is its own index plus the entries of the other list that precede it.  Whole
-// wave; lanes 0 .. K-1 place the result's entries, lanes 32 .. 32+K-1 the arrivals.
+// wave; lanes 0 .. K-1 place the result's entries, lanes 32 .. 32+K-1 the arrivals.  NORM: rs / ns / as hold KEYS, which order
+// the merge, and every entry carries its raw score along (rr -> nr, ar -> nr).
+template <bool NORM>
 __device__ __forceinline__ void kb_arrive(const float* rs, const int* rt, const int* rvr, float* ns, int* nt, int* nvr,
-                                          const float* as, const int* avr, int at, int K, int lane) {
+                                          const float* as, const int* avr, int at, int K, int lane, const float* rr = nullptr,
+                                          float* nr = nullptr, const float* ar = nullptr) {
     if (lane < K) {
         const float s = rs[lane];
         int pos = lane;
@@ -198,6 +208,7 @@ __device__ __forceinline__ void kb_arrive(const float* rs, const int* rt, const 
             ns[pos] = s;
             nt[pos] = rt[lane];
             nvr[pos] = rvr[lane];
+            if (NORM) nr[pos] = rr[lane];
         }
     } else if (lane >= 32 && lane < 32 + K) {
         const int j = lane - 32;
@@ -208,15 +219,27 @@ __device__ __forceinline__ void kb_arrive(const float* rs, const int* rt, const 
             ns[pos] = s;
             nt[pos] = at;
             nvr[pos] = avr[j];
+            if (NORM) nr[pos] = ar[j];
         }
     }
 }
 
-template <int GL, int J, bool STAGED>
+// What the length-normalised form adds to the kernel's arguments: the divisors (NULL = all ones) and the raw scores [B, K].
+struct KbestNorm {
+    const float* len_div;
+    float* raw_scores;
+};
+__device__ __forceinline__ KbestNorm kb_norm(KbestNorm a) { return a; }
+__device__ __forceinline__ KbestNorm kb_norm() { return KbestNorm{nullptr, nullptr}; }
+
+// NormArgs: empty (arcvae_dec_kbest) or one KbestNorm (arcvae_dec_kbest_norm).
+template <int GL, int J, bool STAGED, class... NormArgs>
 __global__ __launch_bounds__(KB_THREADS) void kbest_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
                                                            uint8_t* bp, int32_t* tokens, float* scores, int32_t* lengths, int B,
                                                            int V, int K, int max_len, int min_len, int end_token, int pad_token,
-                                                           float inv_temp) {
+                                                           float inv_temp, NormArgs... norm_args) {
+    constexpr bool NORM = sizeof...(NormArgs) > 0;
+    const KbestNorm na = kb_norm(norm_args...);
     constexpr int GPW = 64 / GL, NG = KB_WAVES * GPW;          // groups per wave; columns per pass of the workgroup
     extern __shared__ __align__(16) float smem[];
     const int V4 = (V + 3) & ~3;
@@ -226,7 +249,9 @@ __global__ __launch_bounds__(KB_THREADS) void kbest_kernel(const float* __restri
     int* res_vr = (int*)(smem + KB_OFF_RES_VR);
     float* arr_s = smem + KB_OFF_ARR_S;
     int* arr_vr = (int*)(smem + KB_OFF_ARR_VR);
-    float* la = smem + KB_OFF_LIST;
+    float* res_r = smem + KB_OFF_RES_R;                        // (NORM only)
+    float* arr_r = smem + KB_OFF_ARR_R;
+    float* la = smem + (NORM ? KB_OFF_LIST_NORM : KB_OFF_LIST);
     float* lb = la + K * V4;
     float* tab = lb + K * V4;
     const int tid = threadIdx.x, lane = tid & 63, l = lane & (GL - 1);
@@ -242,6 +267,7 @@ __global__ __launch_bounds__(KB_THREADS) void kbest_kernel(const float* __restri
             res_s[tid] = -INFINITY;
             res_t[tid] = 0;
             res_vr[tid] = 0;
+            if (NORM) res_r[tid] = -INFINITY;
         }
         __syncthreads();
         if (STAGED) {
@@ -264,7 +290,12 @@ __global__ __launch_bounds__(KB_THREADS) void kbest_kernel(const float* __restri
             const float s = 0.f + lp;
             if (tid == end_token) {
                 if (min_len == 0) {
-                    res_s[0] = s;
+                    if (NORM) {
+                        res_s[0] = s / (na.len_div ? na.len_div[0] : 1.0f);
+                        res_r[0] = s;
+                    } else {
+                        res_s[0] = s;
+                    }
                     res_vr[0] = end_token << 8;
                 }
             } else {
@@ -276,6 +307,7 @@ __global__ __launch_bounds__(KB_THREADS) void kbest_kernel(const float* __restri
         float* nxt = lb;
         int rc = 0;                                            // the result buffer that is current
         for (int t = 1; t < max_len; ++t) {
+            const float div = NORM && na.len_div ? na.len_div[t] : 1.0f;           // (uniform) the divisor of length t + 1
             for (int v0 = 0; v0 < V; v0 += NG) {
                 const int v = v0 + grp;
                 const bool active = v < V;
@@ -293,7 +325,12 @@ __global__ __launch_bounds__(KB_THREADS) void kbest_kernel(const float* __restri
                             bpb[o] = (uint8_t)(oo[h] >> 8);
                             bpb[o + 1] = (uint8_t)oo[h];
                             if (v == end_token) {
-                                arr_s[r] = os[h];
+                                if (NORM) {                    // the lanes that hold the list normalise it: one IEEE division
+                                    arr_s[r] = os[h] / div;
+                                    arr_r[r] = os[h];
+                                } else {
+                                    arr_s[r] = os[h];
+                                }
                                 arr_vr[r] = (end_token << 8) | r;
                             }
                         }
@@ -303,7 +340,8 @@ __global__ __launch_bounds__(KB_THREADS) void kbest_kernel(const float* __restri
                 if (t >= min_len && e >= 0 && e < NG && e / GPW == wave) {
                     kb_wave_lds_order();
                     const int o = rc * KB_MAX_K, n = (rc ^ 1) * KB_MAX_K;
-                    kb_arrive(res_s + o, res_t + o, res_vr + o, res_s + n, res_t + n, res_vr + n, arr_s, arr_vr, t, K, lane);
+                    kb_arrive<NORM>(res_s + o, res_t + o, res_vr + o, res_s + n, res_t + n, res_vr + n, arr_s, arr_vr, t, K, lane,
+                                    res_r + o, res_r + n, arr_r);
                 }
             }
             if (t >= min_len) rc ^= 1;
@@ -325,23 +363,30 @@ __global__ __launch_bounds__(KB_THREADS) void kbest_kernel(const float* __restri
                 for (int h = 0; h < 2; ++h) {
                     const int r = l + 16 * h;
                     if (r < K) {
-                        arr_s[r] = os[h];
+                        if (NORM) {
+                            arr_s[r] = os[h] / (na.len_div ? na.len_div[max_len - 1] : 1.0f);
+                            arr_r[r] = os[h];
+                        } else {
+                            arr_s[r] = os[h];
+                        }
                         arr_vr[r] = oo[h];
                     }
                 }
             }
             kb_wave_lds_order();
             const int o = rc * KB_MAX_K, n = (rc ^ 1) * KB_MAX_K;
-            kb_arrive(res_s + o, res_t + o, res_vr + o, res_s + n, res_t + n, res_vr + n, arr_s, arr_vr, max_len - 1, K, lane);
+            kb_arrive<NORM>(res_s + o, res_t + o, res_vr + o, res_s + n, res_t + n, res_vr + n, arr_s, arr_vr, max_len - 1, K, lane,
+                            res_r + o, res_r + n, arr_r);
         }
         rc ^= 1;
         __syncthreads();
         // back-trace: one thread per returned sequence
         if (tid < K) {
             const float s = res_s[rc * KB_MAX_K + tid];
+            const float raw = NORM ? res_r[rc * KB_MAX_K + tid] : s;       // a slot is empty by its RAW score
             int32_t* out = tokens + ((long)b * K + tid) * max_len;
             int n = 0;
-            if (s > -INFINITY) {                               // (a NaN counts as empty)
+            if (raw > -INFINITY) {                             // (a NaN counts as empty)
                 n = min(max(res_t[rc * KB_MAX_K + tid], 0), max_len - 1) + 1;
                 const int vr = res_vr[rc * KB_MAX_K + tid];
                 int v = min(vr >> 8, V - 1), r = min(vr & 0xff, K - 1);
@@ -355,6 +400,7 @@ __global__ __launch_bounds__(KB_THREADS) void kbest_kernel(const float* __restri
             }
             for (int t = n; t < max_len; ++t) out[t] = pad_token;
             scores[(long)b * K + tid] = n > 0 ? s : -INFINITY;
+            if (NORM) na.raw_scores[(long)b * K + tid] = n > 0 ? raw : -INFINITY;
             lengths[(long)b * K + tid] = n;
         }
         __syncthreads();                                       // the next row reuses the LDS and the slice
@@ -378,11 +424,21 @@ struct KbestArgs {
     int32_t* lengths;
     int B, V, K, max_len, min_len, end_token, pad_token;
     float inv_temp;
+    bool norm;         // the length-normalised form, with:
+    KbestNorm na;
 };
 
 template <int GL, int J, bool STAGED>
 void kbest_launch(const KbestArgs& a, unsigned lds, int grid, hipStream_t stream) {
     // > 64 KB of dynamic LDS has to be allowed per kernel; set on every call (idempotent, no host state kept)
+    if (a.norm) {
+        (void)hipFuncSetAttribute((const void*)kbest_kernel<GL, J, STAGED, KbestNorm>, hipFuncAttributeMaxDynamicSharedMemorySize,
+                                  150 * 1024);
+        hipLaunchKernelGGL((kbest_kernel<GL, J, STAGED, KbestNorm>), dim3(grid), dim3(KB_THREADS), lds, stream, a.logits, a.lse, a.bp,
+                           a.tokens, a.scores, a.lengths, a.B, a.V, a.K, a.max_len, a.min_len, a.end_token, a.pad_token, a.inv_temp,
+                           a.na);
+        return;
+    }
     (void)hipFuncSetAttribute((const void*)kbest_kernel<GL, J, STAGED>, hipFuncAttributeMaxDynamicSharedMemorySize, 150 * 1024);
     hipLaunchKernelGGL((kbest_kernel<GL, J, STAGED>), dim3(grid), dim3(KB_THREADS), lds, stream, a.logits, a.lse, a.bp, a.tokens,
                        a.scores, a.lengths, a.B, a.V, a.K, a.max_len, a.min_len, a.end_token, a.pad_token, a.inv_temp);
@@ -408,17 +464,19 @@ extern "C" int arcvae_dec_kbest_ws_bytes(int B, int V, int K, int max_len, long*
     return ARCVAE_OK;
 }
 
-extern "C" int arcvae_dec_kbest(const float* dense_logits, const float* lse, int32_t* tokens, float* scores, int32_t* lengths,
-                                void* ws, long ws_bytes, int B, int V, int K, int max_len, int min_len, int end_token,
-                                int pad_token, float temperature, hipStream_t stream) {
+namespace {
+
+int kbest_run(const float* dense_logits, const float* lse, int32_t* tokens, float* scores, int32_t* lengths, void* ws, long ws_bytes,
+              int B, int V, int K, int max_len, int min_len, int end_token, int pad_token, float temperature, bool norm,
+              KbestNorm na, hipStream_t stream) {
     if (!dense_logits || !lse || !tokens || !scores || !lengths || !ws || !kbest_dims_ok(B, V, K, max_len)) return ARCVAE_ERR_ARG;
     if (end_token < 0 || end_token >= V || min_len < 0 || min_len > max_len || pad_token < 0 || pad_token > 255) return ARCVAE_ERR_ARG;
     if (!(temperature > 0.f && temperature <= 3.402823466e+38f)) return ARCVAE_ERR_ARG;      // finite and > 0 (a NaN compares false)
     if (ws_bytes < kbest_ws_need(B, V, K, max_len)) return ARCVAE_ERR_ARG;
-    const KbestPlan pl = kbest_plan(V, K);
+    const KbestPlan pl = kbest_plan(V, K, norm);
     const int grid = B < ARCVAE_KBEST_ROWS_IN_FLIGHT ? B : ARCVAE_KBEST_ROWS_IN_FLIGHT;
     const KbestArgs a = {dense_logits, lse, (uint8_t*)ws, tokens, scores, lengths, B, V, K, max_len, min_len, end_token, pad_token,
-                         1.0f / temperature};
+                         1.0f / temperature, norm, na};
     if (pl.GL == 64) {
         if (pl.J == 3) kbest_launch<64, 3, false>(a, pl.lds, grid, stream);
         else kbest_launch<64, 4, false>(a, pl.lds, grid, stream);
@@ -435,4 +493,21 @@ extern "C" int arcvae_dec_kbest(const float* dense_logits, const float* lse, int
         }
     }
     return arcvae_launch_status();
+}
+
+}  // namespace
+
+extern "C" int arcvae_dec_kbest(const float* dense_logits, const float* lse, int32_t* tokens, float* scores, int32_t* lengths,
+                                void* ws, long ws_bytes, int B, int V, int K, int max_len, int min_len, int end_token,
+                                int pad_token, float temperature, hipStream_t stream) {
+    return kbest_run(dense_logits, lse, tokens, scores, lengths, ws, ws_bytes, B, V, K, max_len, min_len, end_token, pad_token,
+                     temperature, false, KbestNorm{nullptr, nullptr}, stream);
+}
+
+extern "C" int arcvae_dec_kbest_norm(const float* dense_logits, const float* lse, const float* len_div, int32_t* tokens,
+                                     float* scores, float* raw_scores, int32_t* lengths, void* ws, long ws_bytes, int B, int V, int K,
+                                     int max_len, int min_len, int end_token, int pad_token, float temperature, hipStream_t stream) {
+    if (!raw_scores) return ARCVAE_ERR_ARG;
+    return kbest_run(dense_logits, lse, tokens, scores, lengths, ws, ws_bytes, B, V, K, max_len, min_len, end_token, pad_token,
+                     temperature, true, KbestNorm{len_div, raw_scores}, stream);
 }

@@ -9,17 +9,21 @@ sampling the reference marks TODO (decoder_sampling.py:115-116): an extension wi
 `generate_beam` (beam search with scores, csrc/beam.hip); `decoder.sequence_log_prob` scores given sequences; and
 `sample=True` with `top_k` / `top_p` (truncated sampling, csrc/sample.hip); and `generate_map` / `token_marginals` /
 `length_distribution`: the exact most probable sequence and the exact per-step token and length distributions of the chain the
-dense table defines (csrc/chain.hip); and `generate_kbest`: the exact K most probable sequences of that chain (csrc/kbest.hip).
+dense table defines (csrc/chain.hip); and `generate_kbest`: the exact K most probable sequences of that chain (csrc/kbest.hip);
+and `length_penalty=` on both (the exact optimum of the length-normalised score), `best_by_length` (the best score of every
+length) and `generate_of_length` (the most probable sequence of a given length).
 
 Every method is its argument checks, the decoder's one path to the table -- `load_conditions`, `dense_table`, `table_lse`,
 `scratch` (models/decoder.py) -- and its own kernel.  What the methods share beyond that is written once below: `_state` +
 `_launch` (the per-key buffers in `self._graphs` and the eager / capture / replay protocol of the two captured walks),
-`_check_lengths`, `_check_chain`, `_table`, `_outputs`, and `_cut` / `_stopped` (early stopping).  A further decoder of the
-table is one method of that shape."""
+`_check_lengths`, `_check_chain`, `_length_divisors`, `_table`, `_outputs`, `_profile`, and `_cut` / `_stopped` (early
+stopping).  A further decoder of the table is one method of that shape."""
 from __future__ import annotations
 
 import ctypes as C
+import math
 
+import numpy as np
 import torch
 
 from arcvae_hip._lib import call, ptr, stream_ptr
@@ -37,6 +41,7 @@ class MLXAutoregressiveDecoderSampling:
         self.latent_dim, self.num_conditions = latent_dim, num_conditions
         self.pad_token, self.end_token = pad_token, end_token
         self._graphs = {}
+        self._divisors = {}
 
     def load_from_decoder(self, other: MLXAutoregressiveDecoder) -> None:
         """Extension (absent in the reference): copy trained decoder weights into the sampler."""
@@ -146,6 +151,36 @@ class MLXAutoregressiveDecoderSampling:
         if self.decoder.vocab_size > 256 or not 0 <= self.end_token < self.decoder.vocab_size:
             raise ValueError("needs vocab_size <= 256 and 0 <= end_token < vocab_size")
 
+    def _length_divisors(self, length_penalty, T: int) -> torch.Tensor:
+        """The [T] float32 device divisors of a length penalty (include/arcvae_hip.h len_div: entry n-1 divides the score of a
+        sequence of n tokens), checked on the host before any device work.  A number alpha -> float(n) ** alpha in float64,
+        rounded to float32 once (kept per (alpha, T) in self._divisors: the host loop and the copy to the device are paid once);
+        a 1-D sequence / array / tensor of T numbers -> as given.  Every divisor must be finite and > 0 as a float32."""
+        key = (length_penalty, T) if type(length_penalty) in (int, float) else None
+        if key in self._divisors:
+            return self._divisors[key]
+        try:
+            if isinstance(length_penalty, torch.Tensor):
+                length_penalty = length_penalty.detach().cpu().numpy()
+            a = np.asarray(length_penalty, dtype=np.float64)
+            if a.ndim == 0:
+                alpha = float(a)
+                if not math.isfinite(alpha):
+                    raise ValueError("length_penalty must be finite")
+                a = np.array([float(n) ** alpha for n in range(1, T + 1)], dtype=np.float64)
+        except (TypeError, ValueError, OverflowError) as e:
+            raise ValueError(f"length_penalty: {e}") from None
+        if a.shape != (T,):
+            raise ValueError("length_penalty must be a number or max_length divisors")
+        with np.errstate(over="ignore", under="ignore"):
+            d = a.astype(np.float32)
+        if not np.all(np.isfinite(d) & (d > 0)):
+            raise ValueError("every length divisor must be finite and > 0 in float32")
+        d = torch.as_tensor(d, device=self.decoder.store.device)
+        if key is not None:
+            self._divisors[key] = d
+        return d
+
     def _table(self, conditions, T: int, temperature: float):
         """(ws, lse [B*V], B): the dense table of `conditions` in ws.logits (mode 0) and its rows' lse at `temperature`."""
         ws, B = self.decoder.load_conditions(conditions, T)
@@ -157,6 +192,55 @@ class MLXAutoregressiveDecoderSampling:
         dev = self.decoder.store.device
         return (torch.empty(*shape, dtype=torch.int32, device=dev), torch.empty(*shape[:-1], dtype=torch.float32, device=dev),
                 torch.empty(*shape[:-1], dtype=torch.int32, device=dev))
+
+    def _profile(self, conditions, T: int, temperature: float):
+        """One forward Viterbi pass that keeps the per-length profile -> (by_length [B, T], open_score [B], scratch, B): the best
+        raw score of any sequence whose first end_token is at position t, the best score of one without, and the back pointers
+        (include/arcvae_hip.h arcvae_dec_viterbi_norm, no divisors)."""
+        self._check_lengths(T, 0)
+        self._check_chain(T, temperature)
+        V, dev = self.decoder.vocab_size, self.decoder.store.device
+        ws, lse, B = self._table(conditions, T, temperature)
+        scratch = self.decoder.scratch("viterbi", B, V, T)
+        tokens, scores, lengths = self._outputs(B, T)
+        raw, by_length, open_score = torch.empty_like(scores), torch.empty(B, T, dtype=torch.float32, device=dev), torch.empty_like(scores)
+        call("arcvae_dec_viterbi_norm", ptr(ws.logits), ptr(lse), None, ptr(tokens), ptr(scores), ptr(raw), ptr(lengths),
+             ptr(by_length), ptr(open_score), ptr(scratch), scratch.numel(), B, V, T, 0, self.end_token, self.pad_token,
+             float(temperature), stream_ptr())
+        return by_length, open_score, scratch, B
+
+    def best_by_length(self, conditions, max_length: int = 80, temperature: float = 1.0):
+        """Extension (absent in the reference): the best-molecule-per-length profile -> (scores [B, max_length] float32,
+        open_score [B] float32).  scores[b, n-1] = the log-probability of the MOST PROBABLE sequence of exactly n tokens that ends
+        with its first end_token there (-inf where there is none), exactly -- the e_t of the Viterbi recursion; open_score = the
+        best sequence of max_length tokens without an end_token (-inf for a one-token vocabulary)."""
+        by_length, open_score, _, _ = self._profile(conditions, int(max_length), temperature)
+        return by_length, open_score
+
+    def generate_of_length(self, conditions, lengths, max_length: int = 80, temperature: float = 1.0):
+        """Extension (absent in the reference): the MOST PROBABLE sequence of exactly lengths[b] tokens (the end_token counts) per
+        row -> (tokens [B, L] int32, L = the longest length asked for; scores [B] float32 = best_by_length at those lengths, equal to
+        decoder.sequence_log_prob of the tokens bit for bit where finite).  lengths: an int, or a [B] sequence / tensor, entries in
+        [1, max_length].  A score of -inf means no such sequence (the end token unreachable); its tokens are then arbitrary.  One
+        forward pass and one back-trace (include/arcvae_hip.h arcvae_dec_viterbi_trace)."""
+        T = int(max_length)
+        if isinstance(lengths, torch.Tensor):
+            lengths = lengths.detach().cpu().numpy()
+        n = np.asarray(lengths)
+        if n.dtype.kind not in "iu" or n.ndim > 1:
+            raise ValueError("lengths must be an int or a [B] sequence of ints")
+        if n.size == 0 or n.min() < 1 or n.max() > T:
+            raise ValueError("need 1 <= lengths <= max_length")
+        if n.ndim == 1 and n.shape[0] != len(conditions):
+            raise ValueError("lengths must have one entry per row")
+        by_length, _, scratch, B = self._profile(conditions, T, temperature)
+        dev = self.decoder.store.device
+        n_d = torch.as_tensor(np.broadcast_to(n, (B,)).astype(np.int32), device=dev)
+        tokens = torch.empty(B, T, dtype=torch.int32, device=dev)
+        call("arcvae_dec_viterbi_trace", ptr(scratch), scratch.numel(), ptr(n_d), ptr(tokens), B, self.decoder.vocab_size, T,
+             self.end_token, self.pad_token, stream_ptr())
+        scores = by_length.gather(1, (n_d.long() - 1)[:, None])[:, 0]
+        return tokens[:, :int(n.max())].contiguous(), scores
 
     def generate_beam(self, z, conditions, max_length: int = 80, beam_width: int = 4, temperature: float = 1.0,
                       min_length: int = 0, early_stopping: bool = True):
@@ -181,41 +265,62 @@ class MLXAutoregressiveDecoderSampling:
         return (_cut(tokens, lengths).contiguous() if early_stopping else tokens), scores
 
     def generate_map(self, z, conditions, max_length: int = 80, temperature: float = 1.0, min_length: int = 0,
-                     early_stopping: bool = True):
+                     early_stopping: bool = True, length_penalty=None):
         """Extension (absent in the reference): the MOST PROBABLE sequence per row under log_softmax(logits / T), exactly -- a
         Viterbi recursion over the dense table (include/arcvae_hip.h arcvae_dec_viterbi) -> (tokens [B, L] int32, scores [B]
         float32).  z is accepted and unused (Q2).  A sequence ends with its first end_token, not before step min_length, or runs
         to max_length without one; positions after the end hold pad_token; ties go to the earliest end, then the lowest tokens.
         early_stopping: L = the longest returned sequence; otherwise L = max_length.  Each score equals
-        decoder.sequence_log_prob of its tokens bit for bit, and is never below generate_beam's best at any width."""
+        decoder.sequence_log_prob of its tokens bit for bit, and is never below generate_beam's best at any width.
+        length_penalty (None = the above, unchanged): a number alpha -> the sequence that maximises log-probability / n ** alpha
+        over ALL admissible sequences, n its number of tokens (the end_token counts), exactly; or max_length divisors, entry n-1
+        for length n.  Returns (tokens, scores, raw_scores): scores the normalised keys, raw_scores the log-probabilities
+        (include/arcvae_hip.h arcvae_dec_viterbi_norm); key ties go to the earliest end."""
         T, min_length = self._check_lengths(max_length, min_length)
         self._check_chain(T, temperature)
+        div = None if length_penalty is None else self._length_divisors(length_penalty, T)
         V = self.decoder.vocab_size
         ws, lse, B = self._table(conditions, T, temperature)
         scratch = self.decoder.scratch("viterbi", B, V, T)
         tokens, scores, lengths = self._outputs(B, T)
+        if div is not None:
+            raw = torch.empty_like(scores)
+            call("arcvae_dec_viterbi_norm", ptr(ws.logits), ptr(lse), ptr(div), ptr(tokens), ptr(scores), ptr(raw), ptr(lengths),
+                 None, None, ptr(scratch), scratch.numel(), B, V, T, min_length, self.end_token, self.pad_token, float(temperature),
+                 stream_ptr())
+            return (_cut(tokens, lengths).contiguous() if early_stopping else tokens), scores, raw
         call("arcvae_dec_viterbi", ptr(ws.logits), ptr(lse), ptr(tokens), ptr(scores), ptr(lengths), ptr(scratch), scratch.numel(),
              B, V, T, min_length, self.end_token, self.pad_token, float(temperature), stream_ptr())
         return (_cut(tokens, lengths).contiguous() if early_stopping else tokens), scores
 
     def generate_kbest(self, z, conditions, max_length: int = 80, num_best: int = 4, temperature: float = 1.0, min_length: int = 0,
-                       early_stopping: bool = True):
+                       early_stopping: bool = True, length_penalty=None):
         """Extension (absent in the reference): the num_best MOST PROBABLE sequences per row under log_softmax(logits / T), exactly
         -- a list-Viterbi recursion over the dense table (include/arcvae_hip.h arcvae_dec_kbest) -> (tokens [B, K, L] int32,
         scores [B, K] float32, descending).  z is accepted and unused (Q2).  Sequences, min_length and padding as in generate_map;
         the K sequences of a row are pairwise distinct, rank 0 is generate_map's, and no rank is below generate_beam's at
         beam_width = num_best.  A slot that no sequence fills (num_best above the number of admissible sequences) has score -inf
         and pad tokens.  early_stopping: L = the longest returned sequence (at least 1); otherwise L = max_length.  Each score
-        equals decoder.sequence_log_prob of its tokens bit for bit; exp(scores).sum(1) is the probability mass the list covers."""
+        equals decoder.sequence_log_prob of its tokens bit for bit; exp(scores).sum(1) is the probability mass the list covers.
+        length_penalty (None = the above, unchanged; values as in generate_map): the K sequences with the largest normalised
+        keys over all admissible sequences, exactly -> (tokens, scores, raw_scores), scores the keys, descending, raw_scores the
+        log-probabilities (include/arcvae_hip.h arcvae_dec_kbest_norm); rank 0 is generate_map's under the same penalty."""
         K = int(num_best)
         if not 1 <= K <= 32:
             raise ValueError("num_best must lie in [1, 32]")
         T, min_length = self._check_lengths(max_length, min_length)
         self._check_chain(T, temperature)
+        div = None if length_penalty is None else self._length_divisors(length_penalty, T)
         V = self.decoder.vocab_size
         ws, lse, B = self._table(conditions, T, temperature)
         scratch = self.decoder.scratch("kbest", B, V, K, T)
         tokens, scores, lengths = self._outputs(B, K, T)
+        if div is not None:
+            raw = torch.empty_like(scores)
+            call("arcvae_dec_kbest_norm", ptr(ws.logits), ptr(lse), ptr(div), ptr(tokens), ptr(scores), ptr(raw), ptr(lengths),
+                 ptr(scratch), scratch.numel(), B, V, K, T, min_length, self.end_token, self.pad_token, float(temperature),
+                 stream_ptr())
+            return (_cut(tokens, lengths, floor=1).contiguous() if early_stopping else tokens), scores, raw
         call("arcvae_dec_kbest", ptr(ws.logits), ptr(lse), ptr(tokens), ptr(scores), ptr(lengths), ptr(scratch), scratch.numel(),
              B, V, K, T, min_length, self.end_token, self.pad_token, float(temperature), stream_ptr())
         return (_cut(tokens, lengths, floor=1).contiguous() if early_stopping else tokens), scores

@@ -33,27 +33,31 @@ class ARCVAE:
 
     def generate(self, batch_size: int, conditions, max_length: int = 80, temperature: float = 1.0, *, sample: bool = False,
                  seed: int = 0, beam_width: Optional[int] = None, top_k: Optional[int] = None,
-                 top_p: Optional[float] = None, exact: bool = False, num_best: Optional[int] = None) -> torch.Tensor:
+                 top_p: Optional[float] = None, exact: bool = False, num_best: Optional[int] = None,
+                 length_penalty=None) -> torch.Tensor:
         """models/vae.py:101-131: z ~ N(0,I) (unused downstream, Q2) -> greedy sampler.  sample / seed (keyword-only extension):
         true categorical sampling instead of the reference's argmax, see MLXAutoregressiveDecoderSampling.  beam_width
         (keyword-only extension): the best hypothesis of a beam search of that width, [B, L] (generate_beam, early stopping).
         top_k / top_p (keyword-only extension, with sample=True): top-k / nucleus truncated sampling.  exact=True (keyword-only
         extension): the most probable sequence of every row, [B, L] (generate_map: exact, where beam search is a heuristic);
         exclusive with sample, beam_width, top_k and top_p.  num_best=K (keyword-only extension, with exact=True): the K most
-        probable sequences of every row, [B, K, L], best first (generate_kbest: exact, where a K-wide beam is a heuristic)."""
+        probable sequences of every row, [B, K, L], best first (generate_kbest: exact, where a K-wide beam is a heuristic).
+        length_penalty (keyword-only extension, with exact=True): the exact optimum (or K best) of log-probability / n ** alpha,
+        or max_length divisors -- see generate_map; tokens only, as without it."""
         dev = self.decoder_sampling.decoder.store.device
         z = torch.randn(batch_size, self.latent_dim, device=dev)
         if num_best is not None and not exact:
             raise ValueError("num_best needs exact=True")
+        if length_penalty is not None and not exact:
+            raise ValueError("length_penalty needs exact=True")
         if exact:
             if sample or beam_width is not None or top_k is not None or top_p is not None:
                 raise ValueError("exact=True is exclusive with sample, beam_width, top_k and top_p")
             if num_best is not None:
-                tokens, _ = self.decoder_sampling.generate_kbest(z, conditions, max_length=max_length, num_best=num_best,
-                                                                 temperature=temperature)
-                return tokens
-            tokens, _ = self.decoder_sampling.generate_map(z, conditions, max_length=max_length, temperature=temperature)
-            return tokens
+                return self.decoder_sampling.generate_kbest(z, conditions, max_length=max_length, num_best=num_best,
+                                                            temperature=temperature, length_penalty=length_penalty)[0]
+            return self.decoder_sampling.generate_map(z, conditions, max_length=max_length, temperature=temperature,
+                                                      length_penalty=length_penalty)[0]
         if beam_width is not None:
             if sample:
                 raise ValueError("beam_width and sample=True are exclusive")
