@@ -625,6 +625,24 @@ int arcvae_adam_step(float* params, const float* grads, float* m, float* v, long
                      const float* partials, long n_partials, double max_norm,                   /* clip part: partials NULL = none   */
                      arcvae_stream_t stream);
 
+/* ---- exponential moving average of the weights (an extension: the reference evaluates and samples the last step's weights) ----
+ * Each entry point is ONE launch over all of a model's flat stores (encoder, decoder, optional predictor): ema / params / a / b
+ * and n are HOST arrays of `segments` device pointers and element counts.
+ * update: for every element of every segment  e = e + fl(omd * fl(p - e)),  omd = (float)one_minus_decay rounded once, every
+ * operation in fp32 in that order, no FMA; `params` is never written.  The caller passes 1 - decay, formed in double, not the
+ * decay: 1 - 0.9999 formed in fp32 is 1.0001659e-4 -- the weight of a new value would be off by 1.7e-4 relative before the first
+ * update.  When either guard word (optional device words, as in arcvae_adam_update) is non-zero at execution time nothing is
+ * written: an update that Adam skipped does not pull the average either.
+ * swap: exchanges the contents of a[i] and b[i] bit for bit; applied twice it is the identity.
+ * Pointers need 4-byte alignment only: a segment whose two pointers are 16-byte aligned takes a float4 main loop and a scalar
+ * tail, any other the scalar loop.  Both keep no host state, allocate nothing and are capture-safe.
+ * ARCVAE_ERR_ARG before any launch: null arrays, segments outside [1, ARCVAE_EMA_MAX_SEGMENTS], an n[i] <= 0, a null pointer in a
+ * used segment; for the update, one_minus_decay outside (0, 1] or not finite. */
+#define ARCVAE_EMA_MAX_SEGMENTS 4
+int arcvae_ema_update(float* const* ema, const float* const* params, const long* n, int segments, double one_minus_decay,
+                      const unsigned* guard_a, const unsigned* guard_b, arcvae_stream_t stream);
+int arcvae_ema_swap(float* const* a, float* const* b, const long* n, int segments, arcvae_stream_t stream);
+
 /* ---- small helpers ---------------------------------------------------------------------------------- */
 int arcvae_colsum_accum(const float* X, int rows, int cols, int ld, float* out, float scale,
                         arcvae_stream_t stream);

@@ -34,6 +34,7 @@ DEC_NO_GPRE = 1024   # arcvae_dec_forward_dense mode bit: forward only, pre-acti
 WGRAD_BF16 = 128     # arcvae_enc_lstm_wgrad parts bit
 WGRAD_QUIET = 512    # arcvae_enc_lstm_wgrad parts bit 9: the per-layer GEMMs on the quiet split-bf16 kernel
 WGRAD_FOLD = 8192    # arcvae_enc_lstm_wgrad parts bit 13: `last` folds with arcvae_table_fold (alone on its outputs)
+EMA_MAX_SEGMENTS = 4  # arcvae_ema_update / arcvae_ema_swap: stores per launch (ARCVAE_EMA_MAX_SEGMENTS)
 
 _vp = C.c_void_p
 _i = C.c_int
@@ -132,6 +133,8 @@ SIGNATURES = {
     "arcvae_adam_update_finalize_clipped": [_vp, _vp, _vp, _vp, _l, _d, _d, _d, _d, _vp, _vp, _vp, _i, _vp, _vp, _i, _i,
                                             _vp, _l, _d, _vp],
     "arcvae_adam_step": [_vp, _vp, _vp, _vp, _l, _vp, _d, _d, _d, _vp, _vp, _vp, _i, _vp, _vp, _i, _i, _vp, _l, _d, _vp],
+    "arcvae_ema_update": [_pp, _pp, _lp, _i, _d, _vp, _vp, _vp],
+    "arcvae_ema_swap": [_pp, _pp, _lp, _i, _vp],
 }
 
 LONG_RESULTS = {"arcvae_enc_lstm_bwd_rs_part_floats"}      # size queries returning `long`; everything else returns an int code

@@ -51,6 +51,36 @@ def data_parallel_of(encoder, decoder):
     return getattr(engine_for(encoder, decoder), "dp", None)
 
 
+def attach_ema(encoder, decoder, ema) -> None:
+    """Tell the pair's data-parallel driver (if any) about a WeightEMA, so that its state broadcast after a replicated step
+    carries the shadows too.  Single process: nothing to do."""
+    dp = data_parallel_of(encoder, decoder)
+    if dp is not None:
+        dp.ema = ema
+
+
+def last_step_guards(encoder, decoder, predictor=None):
+    """The two device error words of the pair's LAST training step (value_and_grad), for a launch that must be skipped
+    together with that step's Adam updates -- the weight EMA (arcvae_hip.ema.WeightEMA.update(guards=)), enqueued on the
+    current stream right behind the step.
+
+    Also where that launch's order behind EVERY Adam update of the step is settled.  Single process: the decoder's update
+    rides on the side stream at the end of the decoder segment; the step's finish on the current stream begins with the
+    join of side -- `Gates.join` (side reports on R behind its decoder segment in stream order; a single-chunk sweep joins
+    with `wait_stream(side)` in encoder_backward) or `wait_stream(side)` in enqueue_finish -- and the encoder's and the
+    predictor's updates are launches of that finish, so whatever follows on the current stream follows all of them.  Data
+    parallel: the decoder's update (`_dec_adam_gated`) runs on side behind the decoder bucket's reduce and main's join on R
+    covers it in the gated form, but `train_step` itself ends with a collective, not with a join of side: the current
+    stream is made to wait for side here, which costs nothing in the step and leaves the drivers untouched."""
+    eng = engine_for(encoder, decoder, predictor)
+    ws = getattr(eng, "last_train_ws", None)
+    if ws is None:
+        raise RuntimeError("last_step_guards: no training step has run for this pair")
+    if getattr(eng, "dp", None) is not None:
+        torch.cuda.current_stream().wait_stream(eng.side)
+    return eng.guards(ws)
+
+
 def draw_coins(T: int, ratio: float) -> np.ndarray:
     """models/decoder.py:180: one np.random.rand() per timestep from the GLOBAL legacy stream, drawn even
     when ratio == 0.0 (validation)."""
@@ -131,10 +161,12 @@ def value_and_grad(encoder, decoder, x, conditions, eps=None, coins=None, teache
         x, conditions = _dev_batch(eng, x, conditions)
         ws = dp.train_step(x, conditions, _local_eps(dp, eps, B), coins, lr, clip_norm=clip, lr_device=lr_device,
                            **hyper)
+        eng.last_train_ws = ws
         return _as_dict(eng, ws, clone=False, status=True, clip=clip is not None, rate=lr_device), (encoder.gradients(), decoder.gradients())
     eng.train_step(x, conditions, eps, coins, lr=lr if lr is not None else 0.0, update=lr is not None, clip_norm=clip,
                    lr_device=lr_device, **hyper)
     ws = eng.workspace(B, T, train=True)
+    eng.last_train_ws = ws       # (last_step_guards)
     out = _as_dict(eng, ws, clone=False, status=True, clip=clip is not None, rate=lr_device)
     if predictor is not None:
         return out, (encoder.gradients(), decoder.gradients(), predictor.gradients())

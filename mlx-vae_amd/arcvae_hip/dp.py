@@ -489,6 +489,7 @@ class EngineDataParallel:
         self.rank, self.world = dist.get_rank(group), dist.get_world_size(group)
         self._drivers = {}
         self._early_group = None
+        self.ema = None          # a WeightEMA whose shadows travel with the state broadcast (api.attach_ema)
 
     def bounds(self, n_rows: int):
         return shard_plan(n_rows, self.rank, self.world)
@@ -499,6 +500,9 @@ class EngineDataParallel:
         for st in (self.eng.enc, self.eng.dec):
             for buf in (st.flat, st.adam_m, st.adam_v):
                 dist.broadcast(buf, src=src, group=self.group)
+        if self.ema is not None:     # the weight EMA's shadows (api.attach_ema): rank 0's, like the weights they follow
+            for name in self.ema.stores:
+                dist.broadcast(self.ema.shadow(name), src=src, group=self.group)
 
     def _load(self, ws, x, cond, eps, coins, lo, hi):
         self.eng.load_inputs(ws, x[lo:hi], cond[lo:hi], None if eps is None else eps[lo:hi], coins)

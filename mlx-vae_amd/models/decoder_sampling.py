@@ -43,9 +43,15 @@ class MLXAutoregressiveDecoderSampling:
         self._graphs = {}
         self._divisors = {}
 
-    def load_from_decoder(self, other: MLXAutoregressiveDecoder) -> None:
-        """Extension (absent in the reference): copy trained decoder weights into the sampler."""
-        self.decoder.store.flat.copy_(other.store.flat)
+    def load_from_decoder(self, other: MLXAutoregressiveDecoder, ema=None) -> None:
+        """Extension (absent in the reference): copy trained decoder weights into the sampler.  ema (an
+        arcvae_hip.ema.WeightEMA that tracks `other` as "decoder"): copy the decoder's averaged weights instead."""
+        if ema is None:
+            self.decoder.store.flat.copy_(other.store.flat)
+            return
+        if ema.stores.get("decoder") is not other.store:
+            raise ValueError("load_from_decoder(ema=): the WeightEMA does not track this decoder's store as 'decoder'")
+        self.decoder.store.flat.copy_(ema.shadow("decoder"))
 
     def parameters(self):
         return {"decoder": self.decoder.parameters()}

@@ -6,7 +6,7 @@ argparse defaults (note Q17: these are the ARGPARSE defaults, not the README's),
 80/10/10 split, checkpoint clearing / `--resume` behaviour, history keys and output files.
 Additive flags: --device, --synthetic N (generate a SELFIES-shaped dataset when the JSON is absent;
 the reference's dataset blob is not distributed), --no_progress, --precision, --world_size / --dist_backend, --grad_clip_mode, --property_predictor_hidden, --lr_schedule /
---warmup_steps / --min_lr_ratio.
+--warmup_steps / --min_lr_ratio, --ema_decay / --ema_warmup / --ema_eval.
 
 Data parallel over the GPUs of one node (the reference is single-process):
     python -m torch.distributed.run --nnodes=1 --nproc-per-node 8 --master-addr 127.0.0.1 --master-port 29544 \
@@ -82,6 +82,14 @@ def build_parser() -> argparse.ArgumentParser:
     ap.add_argument("--warmup_steps", type=int, default=None, help="warmup steps of --lr_schedule (default 0)")
     ap.add_argument("--min_lr_ratio", type=float, default=None, help="final rate of --lr_schedule as a fraction of "
                                                                      "--learning_rate (default 0)")
+    ap.add_argument("--ema_decay", type=float, default=None,
+                    help="keep an exponential moving average of the weights with this decay, 0 < D < 1 (extension; default: "
+                         "none).  Checkpoints then also carry the averaged weights")
+    ap.add_argument("--ema_warmup", action="store_true",
+                    help="ramp the decay of --ema_decay as min(D, (1 + t) / (10 + t)) over the updates t")
+    ap.add_argument("--ema_eval", action="store_true",
+                    help="evaluate (true train loss, validation, latent stats; hence checkpoint_best) on the averaged weights "
+                         "of --ema_decay")
     ap.add_argument("--precision", choices=["fp32", "bf16"], default=None,
                     help="fp32: the parity path (default); bf16: throughput mode -- matrix products on bf16 operands with "
                          "f32 accumulation, parameters and optimizer state in f32 (extension; ARCVAE_PRECISION does the same)")
@@ -127,6 +135,10 @@ def parse_args(argv=None):
     args = ap.parse_args(argv)
     if args.lr_schedule is None and (args.warmup_steps is not None or args.min_lr_ratio is not None):
         ap.error("--warmup_steps / --min_lr_ratio need --lr_schedule")
+    if args.ema_decay is None and (args.ema_warmup or args.ema_eval):
+        ap.error("--ema_warmup / --ema_eval need --ema_decay")
+    if args.ema_decay is not None and not (0.0 < args.ema_decay < 1.0):
+        ap.error("--ema_decay must satisfy 0 < D < 1")
     return args
 
 
@@ -224,7 +236,10 @@ def main(argv=None):
         beta_end=args.beta_end, beta_warmup_epochs=args.beta_warmup_epochs, lambda_prop=args.lambda_prop,
         lambda_collapse=args.lambda_collapse, free_bits=args.free_bits, lambda_mi=args.lambda_mi,
         grad_clip=args.grad_clip, checkpoint_dir=args.checkpoint_dir, progress=not args.no_progress,
-        grad_clip_mode=args.grad_clip_mode, lr_schedule=schedule)
+        grad_clip_mode=args.grad_clip_mode, lr_schedule=schedule, ema_decay=args.ema_decay, ema_warmup=args.ema_warmup,
+        ema_eval=args.ema_eval)
+    if args.ema_decay is not None:
+        print(f"  Weight EMA: decay={args.ema_decay}, warmup={args.ema_warmup}, evaluated={args.ema_eval}")
     if args.resume:
         loaded = trainer.load_checkpoint(str(checkpoint_dir / "checkpoint_best.npz"))
         start_epoch = loaded + 1  # best_val_loss restarts at inf, as in the reference (Q21)

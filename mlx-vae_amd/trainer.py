@@ -29,6 +29,14 @@ word (lr_device=True: the same captured step replays at every rate).  history["l
 epoch's last step, and the checkpoints carry `global_step` and `lr_schedule_json`, so a resumed run continues the curve.
 `lr_schedule=None` (default) is the one-rate trainer, launch for launch, with the checkpoint keys as they are.
 
+Weight EMA (an extension): with `ema_decay=` a decay in (0, 1) the trainer keeps an exponential moving
+average of every module's weights on the device (arcvae_hip.ema.WeightEMA): one launch right behind every step, outside the
+captured step, skipped on the device together with an Adam update that was skipped.  `ema_warmup=True` ramps the decay as
+min(decay, (1 + t) / (10 + t)); `ema_eval=True` runs the epoch's evaluations (true train loss, validation, latent stats) on the
+averaged weights, so the history and train.py's choice of checkpoint_best follow them.  Checkpoints then also carry
+`{tag}_ema_weights/<name>` and `ema_json`; the raw weights stay under their keys, so a resume continues training.
+`ema_decay=None` (default): no EMA object, no launch, no key.
+
 Data parallelism (the reference is single-process): under `torch.distributed` (train.py started by
 `python -m torch.distributed.run`, one process per GPU) every rank runs THIS epoch flow on the same dataset order and the
 same coins (one seeded NumPy stream), every batch is the GLOBAL batch, and the step / the loss forwards work on the
@@ -38,6 +46,7 @@ single-process history; rank 0 alone prints and writes checkpoints / history / p
 """
 from __future__ import annotations
 
+import contextlib
 import json
 from pathlib import Path
 from typing import Dict, Optional, Tuple
@@ -61,7 +70,7 @@ class ARCVAETrainerWithLoss:
                  beta_warmup_epochs: int = 100, lambda_prop: float = 0.1, lambda_collapse: float = 0.01,
                  free_bits: float = 0.5, lambda_mi: float = 0.01, grad_clip: float = 1.0,
                  checkpoint_dir: str = "./checkpoints", progress: bool = True, grad_clip_mode: str = "reference",
-                 lr_schedule=None):
+                 lr_schedule=None, ema_decay: Optional[float] = None, ema_warmup: bool = False, ema_eval: bool = False):
         self.encoder, self.decoder, self.property_predictor = encoder, decoder, property_predictor
         self.dataset, self.batch_size, self.grad_clip = dataset, batch_size, grad_clip
         if grad_clip_mode not in ("reference", "global_norm"):
@@ -99,6 +108,16 @@ class ARCVAETrainerWithLoss:
             "mutual_info")}
         if self.clip_norm is not None:
             self.history["grad_norm"] = []
+        # weight EMA (arcvae_hip/ema.py): None = the trainer as it was, launch for launch
+        if ema_decay is None and (ema_warmup or ema_eval):
+            raise ValueError("ema_warmup / ema_eval need ema_decay")
+        self.ema, self.ema_eval = None, bool(ema_eval)
+        if ema_decay is not None:
+            from arcvae_hip.ema import WeightEMA, check_decay
+            check_decay(ema_decay)
+            self.ema = WeightEMA({tag: mod.store for tag, mod in self._modules()}, ema_decay, warmup=ema_warmup)
+            if self.engine is not None:
+                api.attach_ema(self.encoder, self.decoder, self.ema)
 
     # ---- the three calls into the step engine (tests drive the same epoch flow with oracle-backed ones) ----------
     def _make_engine(self, encoder, decoder):
@@ -121,6 +140,10 @@ class ARCVAETrainerWithLoss:
                                     teacher_forcing_ratio=teacher_forcing_ratio,
                                     lr=self.last_lr if self.lr_schedule is not None else self.learning_rate,
                                     predictor=self.property_predictor, grad_clip=self.clip_norm, **rate, **hyper)
+        if self.ema is not None:
+            # one plain launch on the step's stream, behind every Adam update of the step (api.last_step_guards says why) and
+            # ahead of the per-batch .tolist(): the host never waits for it
+            self.ema.update(guards=api.last_step_guards(self.encoder, self.decoder, self.property_predictor))
         return out["loss_status_norm"] if self.clip_norm is not None else out["loss_and_status"]
 
     def _encode(self, molecules, conditions):
@@ -166,13 +189,19 @@ class ARCVAETrainerWithLoss:
             n += 1
         return {k: (v / n if n > 0 else 0.0) for k, v in tot.items()}
 
+    def _eval_weights(self):
+        """The weights the epoch's evaluations read: the averaged ones inside this context with ema_eval, else the raw ones."""
+        return self.ema.applied() if (self.ema is not None and self.ema_eval) else contextlib.nullcontext()
+
     def _compute_true_train_loss(self, epoch: int, num_batches: int = 10) -> Dict[str, float]:
         """trainer.py:116-175: training loss WITHOUT teacher forcing on the first `num_batches` batches."""
-        return self._eval_batches(self.dataset, self.compute_beta(epoch), num_batches, "True train loss")
+        with self._eval_weights():
+            return self._eval_batches(self.dataset, self.compute_beta(epoch), num_batches, "True train loss")
 
     def _validate(self, val_dataset, beta: float) -> Dict[str, float]:
         """trainer.py:418-487."""
-        return self._eval_batches(val_dataset, beta, None, "Validating")
+        with self._eval_weights():
+            return self._eval_batches(val_dataset, beta, None, "Validating")
 
     # ---- epoch -------------------------------------------------------------------------------------
     def train_epoch(self, epoch: int, total_epochs: int, val_dataset=None) -> Dict[str, float]:
@@ -258,7 +287,8 @@ class ARCVAETrainerWithLoss:
     def _get_latent_stats(self):
         """trainer.py:524-545: encoder pass on the first 64 training rows, printed summary."""
         molecules, conditions = next(iter(self.dataset.to_batches(64, shuffle=False)))
-        mu, logvar = self._encode(molecules, conditions)      # (N ranks: every rank encodes the same 64 rows)
+        with self._eval_weights():
+            mu, logvar = self._encode(molecules, conditions)      # (N ranks: every rank encodes the same 64 rows)
         if self.rank == 0:
             m, lv = mu.cpu().numpy(), logvar.cpu().numpy()
             print(f"   Latent Stats: mu=[{m.min():.3f}, {m.max():.3f}] (mean={m.mean():.3f}, std={m.std():.3f}), "
@@ -297,6 +327,11 @@ class ARCVAETrainerWithLoss:
                 ck[f"{tag}_weights/{n}"] = st.p(n).cpu().numpy()
                 ck[f"{tag}_optimizer_state/m/{n}"] = st._view(st.adam_m, n).cpu().numpy()
                 ck[f"{tag}_optimizer_state/v/{n}"] = st._view(st.adam_v, n).cpu().numpy()
+        if self.ema is not None:     # the averaged weights beside the raw ones (which stay under their keys: a resume trains on)
+            for tag, mod in self._modules():
+                for n in mod.store.names():
+                    ck[f"{tag}_ema_weights/{n}"] = self.ema.shadow_view(tag, n).cpu().numpy()
+            ck["ema_json"] = np.array(json.dumps(self.ema.state()))
         ck["learning_rate"] = np.array(self.learning_rate)
         if self.lr_schedule is not None:
             ck["global_step"] = np.array(self.global_step)
@@ -328,6 +363,17 @@ class ARCVAETrainerWithLoss:
             from lr_schedule import LRSchedule
             self.global_step = int(ck["global_step"])
             self.lr_schedule = LRSchedule.from_state(json.loads(str(ck["lr_schedule_json"])))
+        if self.ema is not None:     # (without an EMA the extra keys of an EMA checkpoint are ignored)
+            if "ema_json" in ck:
+                for tag, mod in self._modules():
+                    for n in mod.store.names():
+                        if f"{tag}_ema_weights/{n}" in ck:
+                            self.ema.shadow_view(tag, n).copy_(torch.from_numpy(ck[f"{tag}_ema_weights/{n}"]))
+                self.ema.load_state(json.loads(str(ck["ema_json"])))
+            else:
+                self.ema.reset()
+                if self.rank == 0:
+                    print("    checkpoint holds no weight EMA: the average restarts from the loaded weights (num_updates = 0)")
         return int(ck["epoch"]) if "epoch" in ck else 0
 
     def save_history(self, path: str):
