@@ -510,6 +510,47 @@ int arcvae_dec_topkp_ws_bytes(int B, int V, int top_k, long* bytes);
 int arcvae_dec_sample_chain_topkp(const float* dense_logits, int32_t* tokens, int32_t* first_end, void* ws, long ws_bytes, int B,
                                   int V, int max_len, int end_token, float temperature, int top_k, float top_p,
                                   const unsigned long long* seed, arcvae_stream_t stream);
+/* EXTENSION (no reference counterpart: the reference decodes greedily) -- sampling WITHOUT replacement over the dense logits
+ * [B*V, V] of arcvae_dec_forward_dense (mode 0): K distinct sequences per batch row that are exactly a sample without replacement
+ * from the sequence distribution arcvae_dec_sample_chain_categorical draws from (stochastic beam search: Kool, van Hoof and Welling,
+ * ICML 2019).  Limits: 1 <= V <= 256, 1 <= K <= 32, B, max_len >= 1, 0 <= pad_token <= 255, temperature > 0, ws_bytes >=
+ * arcvae_dec_swor_ws_bytes(B, K, max_len) (the back pointers), no NULL pointer; anything else (NaN included) is ARCVAE_ERR_ARG before
+ * any launch.  No host state, asynchronous on `stream`, capture-safe, no atomics: repeated calls with one seed are bitwise identical.
+ * arcvae_dec_swor, per batch row b, start token 0, table row b*V + c after token c, lse from arcvae_dec_row_lse:
+ *   Step term  lp(c, v) = fl(x[b*V+c, v] * fl(1.0f / temperature)) - lse[b*V+c], fp32 without contraction (arcvae_dec_beam_search's).
+ *   Log-probability  of a hypothesis: phi, accumulated as fl(phi + lp), one add per step in step order: bit-equal to what
+ *     arcvae_dec_sequence_logprob returns for its tokens.
+ *   Noise  a pure function of (seed, b, token prefix), never of beam slots or launch shape: h_root = mix64(seed ^ (b << 32)),
+ *     h_child = mix64(h_parent + token + 1) in 64-bit wrapping arithmetic, mix64 the splitmix64 finaliser (x += 0x9e3779b97f4a7c15;
+ *     x = (x ^ x >> 30) * 0xbf58476d1ce4e5b9; x = (x ^ x >> 27) * 0x94d049bb133111eb; x ^ x >> 31); n = h_child >> 40,
+ *     u = (n + 0.5) * 2^-24, g = -log(-log(u)).  (n + 0.5 is not an fp32 number for n >= 2^23: there -log(u) is evaluated as
+ *     -log1p(-(2^24 - n - 0.5) * 2^-24), so every u lies strictly inside (0, 1) and g is finite.)  `seed` is a DEVICE pointer to one
+ *     64-bit word, read by the kernel: a captured launch serves every seed.
+ *   Root  phi = 0, perturbed value G = 0.
+ *   Open parent (phi_S, G_S): proposes all V children c: phi_c = phi_S + lp(c), Gp_c = phi_c + g_c, Z = max_c Gp_c, and the
+ *     conditioned value G_c = -log(exp(-G_S) - exp(-Z) + exp(-Gp_c)), evaluated stably as v = G_S - Gp_c + log1p(-exp(Gp_c - Z)),
+ *     G_c = G_S - max(0, v) - log1p(exp(-|v|)); the child that attains Z gets exactly G_S, no child more.  (The kernel forms
+ *     Gp_c - Z and G_S - Gp_c from lp_c + g_c and a carried r = G - phi, so neither cancels numbers of size |phi|.)
+ *   Finished parent (its last token was end_token): absorbing; one continuation, pad_token, phi and G unchanged.
+ *   Selection  the next beam is the K candidates that come first under (G desc, parent slot asc, token asc).
+ *   Threshold  threshold[b] = the running maximum over the steps of the best rejected candidate's G = the (K+1)-th largest
+ *     perturbed value over all complete sequences; -inf if nothing was ever rejected.
+ *   End  when every slot is finished or empty, or at max_len; a sequence still open at max_len is a leaf (the leaves
+ *     arcvae_dec_sample_chain_categorical draws from).
+ *   Outputs  tokens [B, K, max_len] (pad_token after the first end_token), log_probs [B, K] = phi, perturbed [B, K] = G, descending,
+ *     lengths [B, K] (first end_token index + 1, max_len without one), threshold [B].  A slot no sequence fills (K above the number
+ *     of sequences): log_probs = perturbed = -inf, pad tokens, length 0.  The K sequences of a row are pairwise distinct; rank 0 is
+ *     one exact sample and does not depend on K.  Starting the root at G = 0 draws the perturbed values GIVEN that the row's largest
+ *     is 0 (rank 0's perturbed is 0): the sample and its order are exact.  For estimates the conditioning is taken out afterwards,
+ *     exp(-G') = exp(-G) - 1 + E with E ~ Exp(1) (the caller's: E = -log(u) of mix64(h_root) is noise no sequence uses); then, with
+ *     q_k = 1 - exp(-exp(phi_k - threshold')), sum_k exp(phi_k) / q_k * f(x_k) over the ranks above the threshold's is an unbiased
+ *     estimate of E[f].
+ *   Not offered: min_len, top-k / top-p, length penalties -- each changes the measure that is sampled. */
+int arcvae_dec_swor_ws_bytes(int B, int K, int max_len, long* bytes);
+int arcvae_dec_swor(const float* dense_logits, const float* lse, const unsigned long long* seed, int32_t* tokens /*[B,K,max_len]*/,
+                    float* log_probs /*[B,K]*/, float* perturbed /*[B,K]*/, int32_t* lengths /*[B,K]*/, float* threshold /*[B]*/,
+                    void* ws, long ws_bytes, int B, int V, int K, int max_len, int end_token, int pad_token, float temperature,
+                    arcvae_stream_t stream);
 /* Backward of arcvae_dec_forward_dense: embedding.weight, lstm_layer_l.{Wx,bias}, fc_out.{weight,bias}.
  * ws: dh [2,B*V,H], dG [B*V,4H], dtableD [V,4H], wcpart [V,4H,max(C,1)]. */
 int arcvae_dec_backward_dense(const float* emb, const float* const* Wx, const float* const* bias,

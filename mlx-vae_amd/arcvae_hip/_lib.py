@@ -103,6 +103,8 @@ SIGNATURES = {
     "arcvae_dec_topkp_rows": [_vp, _l, _vp, _l, _i, _f, _i, _f, _vp, _vp, _vp, _vp],
     "arcvae_dec_topkp_ws_bytes": [_i, _i, _i, _lp],
     "arcvae_dec_sample_chain_topkp": [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _f, _i, _f, _vp, _vp],
+    "arcvae_dec_swor_ws_bytes": [_i, _i, _i, _lp],
+    "arcvae_dec_swor": [_vp] * 9 + [_l, _i, _i, _i, _i, _i, _i, _f, _vp],
     "arcvae_dec_backward_dense": [_vp, _pp, _pp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,
                                   _pp, _pp, _vp, _vp, _i, _i, _i, _i, _i, _i, _i, _vp],
     "arcvae_reparameterize": [_vp, _vp, _vp, _vp, _l, _vp],

@@ -1,0 +1,264 @@
+// Sampling WITHOUT replacement over the dense decoder table: K distinct sequences per batch row, exactly a sample without
+// replacement from the chain's sequence distribution -- stochastic beam search (Kool, van Hoof and Welling, ICML 2019, the
+// Gumbel-top-k trick).  An EXTENSION with no reference behaviour to match.  Contract: include/arcvae_hip.h (arcvae_dec_swor),
+// restated in NumPy by tests/swor_ref.py.
+//
+// The decoder is stateless per step, so a hypothesis is (batch row, last token) plus what it carries: its
+// log-probability phi, its perturbed value G, r = G - phi, and the hash h of its token prefix, which keys its children's noise.
+// Unlike beam.hip every child carries its own noise, so there are no per-row lists to prepare: a step evaluates all K x V
+// children and selects the first K + 1 of them under (G desc, parent slot asc, token asc) -- K kept, one for the threshold.
+//
+// One workgroup per batch row, one wave per parent (min(K, 16) waves; above 16 parents a wave takes two), a parent's V children
+// up to four per lane (token lane + 64*e: at V = 80 two passes carry children, not four, and the loads are contiguous).
+//   evaluate   a_c = lp_c + g_c; A = wave max; d_c = a_c - A is Gp_c - Z with the parent's phi dropped out; v_c = (r_S - a_c) +
+//              log(1 - exp(d_c)) is G_S - Gp_c + log1p(-exp(Gp_c - Z)): neither difference cancels numbers of size |phi|.
+//              G_c = (G_S - max(0, v)) - log1p(exp(-|v|)) <= G_S in fp32 too, and = G_S for the child that attains A.
+//   select     a candidate is one 64-bit key, (order-preserving image of G) << 16 | (0xFFFF - (slot << 8 | token)): unique, and
+//              descending key order is the contract's order.  Every wave keeps the maximum of the keys it still holds in one
+//              LDS word; a round is: every thread reads the waves' words, the wave that owns the winner publishes the
+//              winner's phi and r (G is in the key), drops the key and finds its new maximum (a lane's own, then a wave
+//              reduction); one barrier.  K + 1 rounds, the last one only reads.
+//   advance    thread j < K builds slot j from winner j and writes the back-pointer (parent | token << 8), as beam.hip.
+// No atomics, no dependence on launch shape: the noise is a function of (seed, batch row, token prefix) only.
+#include "common.h"
+
+namespace {
+
+constexpr int SWOR_MAX_K = 32;
+constexpr int SWOR_MAX_V = 256;
+constexpr int SWOR_MAX_WAVES = 16;           // 1024 threads; parents above 16 go to a wave's second pass
+constexpr int SWOR_PASSES = SWOR_MAX_K / SWOR_MAX_WAVES;
+
+__device__ __forceinline__ unsigned long long swor_key(float G, int slot, int token) {
+    if (G == 0.f) G = 0.f;                                // -0 == +0: one key
+    const unsigned u = __float_as_uint(G);
+    const unsigned k32 = (u & 0x80000000u) ? ~u : (u | 0x80000000u);
+    return ((unsigned long long)k32 << 16) | (unsigned long long)(0xFFFF - ((slot << 8) | token));
+}
+
+__device__ __forceinline__ float swor_key_value(unsigned long long key) {
+    const unsigned k32 = (unsigned)(key >> 16);
+    return __uint_as_float((k32 & 0x80000000u) ? (k32 & 0x7fffffffu) : ~k32);
+}
+
+// g = -log(-log(u)), u = (n + 0.5) * 2^-24, n the hash's top 24 bits.  n + 0.5 is not an fp32 number for n >= 2^23; there
+// -log(u) = -log1p(-(2^24 - n - 0.5) * 2^-24), whose argument is one.  Every u lies in (0, 1): g is finite.
+__device__ __forceinline__ float swor_gumbel(unsigned long long h) {
+    const unsigned n = (unsigned)(h >> 40);
+    const float e = n >= (1u << 23) ? -log1pf(-(((float)((1u << 24) - n) - 0.5f) * 0x1p-24f))
+                                    : -logf(((float)n + 0.5f) * 0x1p-24f);
+    return -logf(e);
+}
+
+__device__ __forceinline__ unsigned long long swor_wave_max(unsigned long long v) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        const unsigned long long other = __shfl_xor(v, o, 64);
+        v = other > v ? other : v;
+    }
+    return v;
+}
+
+__device__ __forceinline__ unsigned long long swor_lane_max(const unsigned long long (&key)[SWOR_PASSES][4]) {
+    unsigned long long m = 0ull;
+#pragma unroll
+    for (int q = 0; q < SWOR_PASSES; ++q)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) m = key[q][e] > m ? key[q][e] : m;
+    return m;
+}
+
+// Slot state (LDS): st 0 = empty, 1 = open, 2 = finished (its last token was end_token); tok = last token; phi, G, r, h.
+__global__ __launch_bounds__(1024) void swor_walk_kernel(const float* __restrict__ logits, const float* __restrict__ lse,
+                                                         const unsigned long long* __restrict__ seed_ptr, uint16_t* bp,
+                                                         int32_t* tokens, float* log_probs, float* perturbed, int32_t* lengths,
+                                                         float* threshold, int V, int K, int max_len, int end_token,
+                                                         int pad_token, float inv_temp) {
+    __shared__ float s_phi[SWOR_MAX_K], s_G[SWOR_MAX_K], s_r[SWOR_MAX_K], n_phi[SWOR_MAX_K], n_r[SWOR_MAX_K];
+    __shared__ unsigned long long s_h[SWOR_MAX_K], sel[SWOR_MAX_K], wmax[2][SWOR_MAX_WAVES];
+    __shared__ int s_tok[SWOR_MAX_K], s_st[SWOR_MAX_K];
+    const int tid = threadIdx.x, lane = tid & 63, w = tid >> 6, nw = blockDim.x >> 6, b = blockIdx.x;
+    if (tid < K) {
+        s_phi[tid] = s_G[tid] = tid == 0 ? 0.f : -INFINITY;
+        s_r[tid] = 0.f;
+        s_h[tid] = tid == 0 ? mix64(*seed_ptr ^ ((unsigned long long)b << 32)) : 0ull;
+        s_tok[tid] = 0;                                   // start token 0, as the greedy walk
+        s_st[tid] = tid == 0 ? 1 : 0;
+    }
+    __syncthreads();
+    float thr = -INFINITY;                                // block-uniform
+    int t_end = max_len;
+    for (int t = 0; t < max_len; ++t) {
+        // 1. evaluate: this wave's parents' children
+        unsigned long long key[SWOR_PASSES][4];
+        float cphi[SWOR_PASSES][4], cr[SWOR_PASSES][4];
+#pragma unroll
+        for (int q = 0; q < SWOR_PASSES; ++q) {
+#pragma unroll
+            for (int e = 0; e < 4; ++e) {
+                key[q][e] = 0ull;                         // 0 = no candidate (a real key's upper part is never 0)
+                cphi[q][e] = cr[q][e] = 0.f;
+            }
+            const int p = w + q * nw;
+            if (p >= K) continue;                         // wave-uniform
+            const int st = s_st[p];
+            const float phiS = s_phi[p], GS = s_G[p], rS = s_r[p];
+            if (st == 2) {                                // EOS is absorbing: one continuation, pad, unchanged
+                if (lane == 0) {
+                    key[q][0] = swor_key(GS, p, pad_token);
+                    cphi[q][0] = phiS;
+                    cr[q][0] = rS;
+                }
+            } else if (st == 1) {
+                const long row = (long)b * V + s_tok[p];
+                const float* x = logits + row * V;
+                const float l = lse[row];
+                const unsigned long long hS = s_h[p];
+                float a[4], lp[4];
+                float amax = -INFINITY;
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int j = lane + 64 * e;          // (64 * e >= V: no lane has a child, the math is skipped wave-wide)
+                    a[e] = -INFINITY;
+                    lp[e] = 0.f;
+                    if (j < V) {
+                        const float xs = x[j] * inv_temp;
+                        lp[e] = xs - l;
+                        a[e] = lp[e] + swor_gumbel(mix64(hS + (unsigned long long)j + 1ull));
+                    }
+                    amax = fmaxf(amax, a[e]);
+                }
+                amax = wave_max(amax);
+#pragma unroll
+                for (int e = 0; e < 4; ++e) {
+                    const int j = lane + 64 * e;
+                    if (j >= V) continue;
+                    const float d = a[e] - amax;
+                    const float lg = d > -0.6931471805599453f ? logf(-expm1f(d)) : log1pf(-expf(d));
+                    const float v = (rS - a[e]) + lg;
+                    const float hi = fmaxf(v, 0.f), lo = log1pf(expf(-fabsf(v)));
+                    key[q][e] = swor_key((GS - hi) - lo, p, j);
+                    cr[q][e] = ((rS - lp[e]) - hi) - lo;
+                    cphi[q][e] = phiS + lp[e];
+                }
+            }
+        }
+        // 2. select: round i = the largest key left.  Only the wave that owned round i-1's winner has a new maximum to find;
+        //    the others hand their old one on (wmax is double-buffered: one barrier per round)
+        unsigned long long m = swor_lane_max(key);
+        m = swor_wave_max(m);
+        if (lane == 0) wmax[0][w] = m;
+        __syncthreads();
+        unsigned long long rejected = 0ull;
+        int filled = 0;
+        for (int rd = 0; rd <= K; ++rd) {
+            unsigned long long best = 0ull;
+            for (int i = 0; i < nw; ++i) {
+                const unsigned long long o = wmax[rd & 1][i];
+                best = o > best ? o : best;
+            }
+            if (best == 0ull) break;                      // no candidate left (block-uniform)
+            if (rd == K) {
+                rejected = best;
+                break;
+            }
+            ++filled;
+            if (m == best) {                              // wave-uniform; keys are unique: one wave, one lane of it
+#pragma unroll
+                for (int q = 0; q < SWOR_PASSES; ++q)
+#pragma unroll
+                    for (int e = 0; e < 4; ++e)
+                        if (key[q][e] == best) {
+                            sel[rd] = best;
+                            n_phi[rd] = cphi[q][e];
+                            n_r[rd] = cr[q][e];
+                            key[q][e] = 0ull;             // taken
+                        }
+                m = swor_wave_max(swor_lane_max(key));
+            }
+            if (lane == 0) wmax[(rd + 1) & 1][w] = m;
+            __syncthreads();
+        }
+        if (rejected != 0ull) thr = fmaxf(thr, swor_key_value(rejected));
+        __syncthreads();
+        // 3. advance: slot j from winner j
+        float phiN = -INFINITY, GN = -INFINITY, rN = 0.f;
+        unsigned long long hN = 0ull;
+        int tokN = pad_token, stN = 0, par = 255;
+        if (tid < filled) {
+            const unsigned long long k = sel[tid];
+            const int id = 0xFFFF - (int)(k & 0xFFFFull);
+            par = min(id >> 8, K - 1);
+            tokN = id & 255;
+            GN = swor_key_value(k);
+            phiN = n_phi[tid];
+            rN = n_r[tid];
+            const bool was_done = s_st[par] == 2;
+            hN = was_done ? s_h[par] : mix64(s_h[par] + (unsigned long long)tokN + 1ull);
+            stN = (was_done || tokN == end_token) ? 2 : 1;
+        }
+        __syncthreads();
+        if (tid < K) {
+            s_phi[tid] = phiN;
+            s_G[tid] = GN;
+            s_r[tid] = rN;
+            s_h[tid] = hN;
+            s_tok[tid] = tokN;
+            s_st[tid] = stN;
+            bp[((long)b * max_len + t) * K + tid] = (uint16_t)((par & 255) | ((tokN & 255) << 8));
+        }
+        // every hypothesis finished (or empty): the remaining steps would copy each slot onto itself with a pad token
+        if (!__syncthreads_or(tid < K && stN == 1)) {
+            t_end = t + 1;
+            break;
+        }
+    }
+    // 4. backtrack
+    if (tid == 0) threshold[b] = thr;
+    if (tid < K) {
+        const float phi = s_phi[tid];
+        int32_t* out = tokens + ((long)b * K + tid) * max_len;
+        log_probs[(long)b * K + tid] = phi;
+        perturbed[(long)b * K + tid] = s_G[tid];
+        for (int t = t_end; t < max_len; ++t) out[t] = pad_token;
+        if (s_st[tid] == 0) {
+            for (int t = 0; t < t_end; ++t) out[t] = pad_token;
+            lengths[(long)b * K + tid] = 0;
+        } else {
+            int slot = tid, fe = max_len;
+            for (int t = t_end - 1; t >= 0; --t) {
+                const uint16_t v = bp[((long)b * max_len + t) * K + slot];
+                const int tok = v >> 8;
+                out[t] = tok;
+                if (tok == end_token) fe = t;
+                slot = min((int)(v & 255), K - 1);
+            }
+            lengths[(long)b * K + tid] = fe < max_len ? fe + 1 : max_len;
+        }
+    }
+}
+
+long swor_ws_bytes(int B, int K, int max_len) { return (long)B * max_len * K * 2; }   // bp [B, max_len, K] u16
+
+}  // namespace
+
+extern "C" int arcvae_dec_swor_ws_bytes(int B, int K, int max_len, long* bytes) {
+    if (!bytes || B <= 0 || K < 1 || K > SWOR_MAX_K || max_len <= 0) return ARCVAE_ERR_ARG;
+    *bytes = swor_ws_bytes(B, K, max_len);
+    return ARCVAE_OK;
+}
+
+extern "C" int arcvae_dec_swor(const float* dense_logits, const float* lse, const unsigned long long* seed, int32_t* tokens,
+                               float* log_probs, float* perturbed, int32_t* lengths, float* threshold, void* ws, long ws_bytes,
+                               int B, int V, int K, int max_len, int end_token, int pad_token, float temperature,
+                               hipStream_t stream) {
+    if (!dense_logits || !lse || !seed || !tokens || !log_probs || !perturbed || !lengths || !threshold || !ws)
+        return ARCVAE_ERR_ARG;
+    if (B <= 0 || V <= 0 || V > SWOR_MAX_V || K < 1 || K > SWOR_MAX_K || max_len <= 0) return ARCVAE_ERR_ARG;
+    if (pad_token < 0 || pad_token > 255 || !(temperature > 0.f)) return ARCVAE_ERR_ARG;   // bp keeps a token in 8 bits
+    if (ws_bytes < swor_ws_bytes(B, K, max_len)) return ARCVAE_ERR_ARG;
+    const int waves = K < SWOR_MAX_WAVES ? K : SWOR_MAX_WAVES;
+    hipLaunchKernelGGL(swor_walk_kernel, dim3(B), dim3(64 * waves), 0, stream, dense_logits, lse, seed, (uint16_t*)ws, tokens,
+                       log_probs, perturbed, lengths, threshold, V, K, max_len, end_token, pad_token, 1.0f / temperature);
+    return arcvae_launch_status();
+}

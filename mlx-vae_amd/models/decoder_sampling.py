@@ -11,7 +11,8 @@ sampling the reference marks TODO (decoder_sampling.py:115-116): an extension wi
 `length_distribution`: the exact most probable sequence and the exact per-step token and length distributions of the chain the
 dense table defines (csrc/chain.hip); and `generate_kbest`: the exact K most probable sequences of that chain (csrc/kbest.hip);
 and `length_penalty=` on both (the exact optimum of the length-normalised score), `best_by_length` (the best score of every
-length) and `generate_of_length` (the most probable sequence of a given length).
+length) and `generate_of_length` (the most probable sequence of a given length); and `generate_without_replacement`: K distinct
+random sequences per row, exactly a sample without replacement, with `importance_weights` for unbiased estimates (csrc/swor.hip).
 
 Every method is its argument checks, the decoder's one path to the table -- `load_conditions`, `dense_table`, `table_lse`,
 `scratch` (models/decoder.py) -- and its own kernel.  What the methods share beyond that is written once below: `_state` +
@@ -331,6 +332,61 @@ class MLXAutoregressiveDecoderSampling:
              B, V, K, T, min_length, self.end_token, self.pad_token, float(temperature), stream_ptr())
         return (_cut(tokens, lengths, floor=1).contiguous() if early_stopping else tokens), scores
 
+    def generate_without_replacement(self, z, conditions, max_length: int = 80, num_samples: int = 4, temperature: float = 1.0,
+                                     seed: int = 0, early_stopping: bool = True, use_graph: bool = True, *,
+                                     return_weights: bool = False):
+        """Extension (absent in the reference): num_samples DISTINCT random sequences per row -- exactly a sample without
+        replacement from the sequence distribution sample=True draws from at this temperature (stochastic beam search,
+        include/arcvae_hip.h arcvae_dec_swor) -> (tokens [B, K, L] int32, log_probs [B, K] float32, perturbed [B, K] float32,
+        descending, threshold [B] float32).  z is accepted and unused (Q2).  Rank 0 is one exact sample and does not depend on
+        num_samples; the noise is keyed by (seed, row, token prefix): the same seed returns the same molecules.  Positions after
+        a sequence's first end_token hold pad_token; a slot that no sequence fills (num_samples above the number of sequences) has
+        log_probs = perturbed = -inf and pad tokens.  Each log_prob equals decoder.sequence_log_prob of its tokens bit for bit.
+        threshold = the (K+1)-th largest perturbed value (-inf when nothing was left out).  perturbed and threshold are drawn
+        given that the row's largest perturbed value is 0 (rank 0's is 0); `unconditioned` takes that conditioning out, and
+        importance_weights(log_probs, unconditioned(threshold, seed)) are the inclusion-corrected weights.  return_weights=True
+        appends weights [B, K]: the weights of the unbiased estimator sum_k weights[:, k] * f(x_k) of E_model[f(x)] -- the K-1
+        highest ranks against the K-th sequence's unconditioned perturbed value, column K-1 zero (it needs num_samples >= 2).  early_stopping: L = the longest returned sequence (at least 1); otherwise L =
+        max_length.  min_length, top_k / top_p and length penalties are not offered: each changes the measure that is sampled.
+        The seed is read by the kernel from a device word written before the launch, so the pass (dense table, its lse, the walk)
+        is captured once per (B, max_length, temperature, num_samples) and replayed for every seed; use_graph=False launches the
+        same kernels eagerly."""
+        K = int(num_samples)
+        if not 1 <= K <= 32:
+            raise ValueError("num_samples must lie in [1, 32]")
+        T, _ = self._check_lengths(max_length, 0)
+        self._check_chain(T, temperature)
+        dec = self.decoder
+        V, dev = dec.vocab_size, dec.store.device
+        ws, B = dec.load_conditions(conditions, T)              # (the copy stays outside the captured pass, as in _table)
+
+        def buffers():
+            tokens, log_probs, lengths = self._outputs(B, K, T)
+            return dict(seed=torch.zeros(1, dtype=torch.int64, device=dev), scratch=dec.scratch("swor", B, K, T),
+                        lse=torch.empty(B * V, dtype=torch.float32, device=dev), out=tokens, log_probs=log_probs,
+                        lengths=lengths, perturbed=torch.empty_like(log_probs),
+                        threshold=torch.empty(B, dtype=torch.float32, device=dev))
+
+        st = self._state(("swor", B, T, float(temperature), K), B, 1, buffers)
+        s64 = int(seed) & 0xFFFFFFFFFFFFFFFF
+        st["seed"].fill_(s64 - (1 << 64) if s64 >= 1 << 63 else s64)       # the 64-bit word the kernel reads
+
+        def enqueue():
+            dec.dense_table(ws)
+            call("arcvae_dec_row_lse", ptr(ws.logits), ptr(st["lse"]), B * V, V, float(temperature), stream_ptr())
+            call("arcvae_dec_swor", ptr(ws.logits), ptr(st["lse"]), ptr(st["seed"]), ptr(st["out"]), ptr(st["log_probs"]),
+                 ptr(st["perturbed"]), ptr(st["lengths"]), ptr(st["threshold"]), ptr(st["scratch"]), st["scratch"].numel(), B, V, K,
+                 T, self.end_token, self.pad_token, float(temperature), stream_ptr())
+
+        _launch(st, enqueue, use_graph)
+        tokens = (_cut(st["out"], st["lengths"], floor=1) if early_stopping else st["out"]).clone()
+        log_probs, perturbed, threshold = st["log_probs"].clone(), st["perturbed"].clone(), st["threshold"].clone()
+        if not return_weights:
+            return tokens, log_probs, perturbed, threshold
+        weights = importance_weights(log_probs, unconditioned(perturbed[:, K - 1], seed))
+        weights[:, K - 1] = 0.0
+        return tokens, log_probs, perturbed, threshold, weights
+
     def token_marginals(self, conditions, max_length: int = 80, temperature: float = 1.0) -> torch.Tensor:
         """Extension (absent in the reference): [B, max_length, V] float32, entry [b, t, v] = P(the token at step t is v and no
         end_token came before t) of what sample=True draws at this temperature -- the chain's forward recursion, exact up to fp32
@@ -350,6 +406,45 @@ class MLXAutoregressiveDecoderSampling:
         last = alive[:, -1, :]
         rest = last.sum(dim=1) - last[:, self.end_token]
         return torch.cat([alive[:, :, self.end_token], rest[:, None]], dim=1)
+
+
+def importance_weights(log_probs: torch.Tensor, threshold: torch.Tensor) -> torch.Tensor:
+    """The weights exp(log_probs) / q of sequences sampled WITHOUT replacement (generate_without_replacement), [B, K] like
+    log_probs: q = -expm1(-exp(log_probs - threshold[:, None])) is the probability that a sequence's perturbed value exceeds
+    `threshold` [B].  exp(log_probs) where threshold is -inf (every sequence is included: q = 1); 0 for unfilled slots (log_probs
+    -inf).  With threshold = the K-th sequence's UNCONDITIONED perturbed value (`unconditioned`), sum_k w_k f(x_k) over the K-1
+    highest-ranked sequences is an UNBIASED estimator of E_model[f(x)] (Kool et al. 2019, section 4.2); these are the weights
+    generate_without_replacement(return_weights=True) returns.  The values the walk returns are conditioned on the row's largest
+    being 0; used as they are they give weights that are too small (the sum of the weights then averages E[(K-1) / (1 + Gamma(K-1))]
+    instead of 1).  Evaluated in float64, returned in log_probs' dtype."""
+    lp, thr = log_probs.double(), threshold.double()[:, None]
+    e = torch.exp(lp - thr)                                     # (+inf at threshold -inf: q = 1)
+    q = -torch.expm1(-e)
+    w = torch.where(q > 0, torch.exp(lp) / q, torch.exp(thr).expand_as(lp))      # e underflows: exp(lp) / q -> exp(threshold)
+    return torch.where(torch.isneginf(lp), torch.zeros_like(w), w).to(log_probs.dtype)
+
+
+def _mix64(x: np.ndarray) -> np.ndarray:
+    """splitmix64 finaliser (csrc/common.h mix64) on a uint64 array."""
+    x = x + np.uint64(0x9E3779B97F4A7C15)
+    x = (x ^ (x >> np.uint64(30))) * np.uint64(0xBF58476D1CE4E5B9)
+    x = (x ^ (x >> np.uint64(27))) * np.uint64(0x94D049BB133111EB)
+    return x ^ (x >> np.uint64(31))
+
+
+def unconditioned(values: torch.Tensor, seed: int) -> torch.Tensor:
+    """Perturbed values or thresholds of generate_without_replacement ([B] or [B, K], row b of the batch first) with the
+    conditioning on the row's maximum taken out.  The walk starts every row at G = 0, i.e. it draws the perturbed values GIVEN that
+    the largest of the row is 0: that leaves the sample and its order exact, but the estimator of importance_weights needs the
+    values themselves.  As arrival times exp(-G) of a Poisson process the conditioning is a shift of the first arrival, so
+    exp(-G') = exp(-G) - 1 + E with E ~ Exp(1) the row's largest value's own time: here E = -log(u) from the hash of the row's
+    empty prefix, u = ((mix64(mix64(seed ^ (b << 32))) >> 40) + 0.5) * 2^-24 -- noise no sequence uses, a function of (seed, row).
+    Monotone: the order, and -inf, are kept.  float64 inside, returned in values' dtype."""
+    B = values.shape[0]
+    h = _mix64(_mix64(np.uint64(int(seed) & 0xFFFFFFFFFFFFFFFF) ^ (np.arange(B, dtype=np.uint64) << np.uint64(32))))
+    E = -np.log(((h >> np.uint64(40)).astype(np.float64) + 0.5) * 2.0 ** -24)
+    E = torch.as_tensor(E, device=values.device).reshape((B,) + (1,) * (values.dim() - 1))
+    return (-torch.log(torch.expm1(-values.double()) + E)).to(values.dtype)
 
 
 def _launch(st: dict, enqueue, use_graph: bool) -> None:

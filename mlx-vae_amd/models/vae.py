@@ -34,7 +34,7 @@ class ARCVAE:
     def generate(self, batch_size: int, conditions, max_length: int = 80, temperature: float = 1.0, *, sample: bool = False,
                  seed: int = 0, beam_width: Optional[int] = None, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, exact: bool = False, num_best: Optional[int] = None,
-                 length_penalty=None) -> torch.Tensor:
+                 length_penalty=None, num_samples: Optional[int] = None) -> torch.Tensor:
         """models/vae.py:101-131: z ~ N(0,I) (unused downstream, Q2) -> greedy sampler.  sample / seed (keyword-only extension):
         true categorical sampling instead of the reference's argmax, see MLXAutoregressiveDecoderSampling.  beam_width
         (keyword-only extension): the best hypothesis of a beam search of that width, [B, L] (generate_beam, early stopping).
@@ -43,9 +43,18 @@ class ARCVAE:
         exclusive with sample, beam_width, top_k and top_p.  num_best=K (keyword-only extension, with exact=True): the K most
         probable sequences of every row, [B, K, L], best first (generate_kbest: exact, where a K-wide beam is a heuristic).
         length_penalty (keyword-only extension, with exact=True): the exact optimum (or K best) of log-probability / n ** alpha,
-        or max_length divisors -- see generate_map; tokens only, as without it."""
+        or max_length divisors -- see generate_map; tokens only, as without it.  num_samples=K (keyword-only extension, with
+        sample=True): K DISTINCT random sequences of every row, [B, K, L] -- a sample without replacement
+        (generate_without_replacement, seeded by `seed`); exclusive with beam_width, exact, top_k and top_p."""
         dev = self.decoder_sampling.decoder.store.device
         z = torch.randn(batch_size, self.latent_dim, device=dev)
+        if num_samples is not None:
+            if not sample:
+                raise ValueError("num_samples needs sample=True")
+            if exact or beam_width is not None or top_k is not None or top_p is not None:
+                raise ValueError("num_samples is exclusive with beam_width, exact, top_k and top_p")
+            return self.decoder_sampling.generate_without_replacement(z, conditions, max_length=max_length, num_samples=num_samples,
+                                                                      temperature=temperature, seed=seed)[0]
         if num_best is not None and not exact:
             raise ValueError("num_best needs exact=True")
         if length_penalty is not None and not exact:
