@@ -369,8 +369,8 @@ int arcvae_dec_sample_chain_categorical(const float* dense_logits, int32_t* toke
  * Limits  B, max_len >= 1; 1 <= V <= 256 (a token fits in a byte); 1 <= K <= 32 where there is a K; 0 <= pad_token <= 255 and
  *   0 <= min_len <= max_len where there is one; temperature > 0; ws_bytes at least the entry point's *_ws_bytes query (caller-owned
  *   device scratch); no NULL pointer but those marked.  Anything else (a NaN included) is ARCVAE_ERR_ARG before any launch.
- *   Two limits differ, on purpose or by history: arcvae_dec_viterbi* / _chain_marginals / _kbest* index by end_token and want
- *   0 <= end_token < V and a FINITE temperature; the others only compare end_token (any value; one outside [0, V) never matches)
+ *   Two limits differ, on purpose or by history: arcvae_dec_viterbi* / _chain_marginals / _chain_expect / _kbest* index by
+ *   end_token and want 0 <= end_token < V and a FINITE temperature (arcvae_dec_row_costs: finite temperatures); the others only compare end_token (any value; one outside [0, V) never matches)
  *   and take temperature = +inf (inv_temp = 0: every row uniform).
  * Tie order  where candidates are ordered through an integer key, the key is the order-preserving image of the fp32 value, then
  *   the complement of the index: value descending, index ascending.  -0 == +0 but their images differ: top-k / top-p and
@@ -423,6 +423,31 @@ int arcvae_dec_viterbi(const float* dense_logits, const float* lse, int32_t* tok
                        arcvae_stream_t stream);
 int arcvae_dec_chain_marginals(const float* dense_logits, const float* lse, float* alive, int B, int V, int max_len, int end_token,
                                float temperature, arcvae_stream_t stream);
+/* Exact expectations over the chain's OUTCOMES: entropy, cross-entropy, expected token counts and length, the mass max_len cuts
+ * off -- closed forms on the forward recursion of arcvae_dec_chain_marginals (same p, same alive, same limits: 0 <= end_token < V,
+ * finite temperatures); nothing is sampled and alive is not written to memory.
+ * An outcome of row b is a sequence up to and including its first end_token, of length n <= max_len, or max_len tokens without
+ * one.  For a per-state cost r[b, u] the expected total over an outcome of sum_t r(fed_t), fed_0 = 0, fed_t = x_{t-1}, is
+ *   total_r[b] = r[b, 0] + sum over v != end_token of r[b, v] * cont[b, v],  cont[b, v] = sum_{t=0}^{max_len-2} alive[b, t, v]
+ *   (the start row always counts, also when end_token == 0; the last step's tokens are never fed back).
+ * arcvae_dec_row_costs: the costs of the R = B*V table rows.  h[r] = -sum_v p(r, v) * lp(r, v), the row's entropy: by the chain
+ *   rule total_h is the entropy of the outcome distribution, in nats.  With a second table q (logits_q, lse_q from
+ *   arcvae_dec_row_lse at temperature_q; same R and V; other conditions, another temperature or other weights)
+ *   c[r] = -sum_v p(r, v) * lq(r, v): total_c is the cross-entropy -E_P[log Q] and KL(P || Q) = fl(total_c - total_h), not clamped:
+ *   rounding may leave it slightly negative.  q is logits_q, lse_q and c: all three NULL or all three given; temperature_q is
+ *   checked either way.  p = expf(lp) is formed once and a term whose p is 0 is skipped (its logarithm may be -inf; 0 * inf is
+ *   not relied on).  h and c accumulate in the same loop by the same operations and the same fixed butterfly, so a q that is the
+ *   p table at the same lse and temperature gives c == h bit for bit, hence total_c == total_h and a KL of exactly 0.
+ * arcvae_dec_chain_expect: n_cost (0 .. 4) per-state costs, cost [n_cost, B*V] -> totals [B, n_cost] (cost and totals NULL iff
+ *   n_cost == 0; a state whose cont is 0 contributes 0 whatever its cost holds); visits [B, V] or NULL: visits[b, v] =
+ *   sum_{t=0}^{max_len-1} alive[b, t, v], the expected number of times v is emitted -- column end_token is P(ended within max_len)
+ *   and the sum over v is the expected length, an open outcome counting max_len; open_mass [B] or NULL: the sum over
+ *   v != end_token of alive[b, max_len-1, v].  At least one output must be asked for; an output whose pointer is NULL is not
+ *   touched.  fp32 sums in the kernel's own, fixed order: repeated calls are bitwise identical. */
+int arcvae_dec_row_costs(const float* logits_p, const float* lse_p, float temperature_p, const float* logits_q, const float* lse_q,
+                         float temperature_q, float* h, float* c, long R, int V, arcvae_stream_t stream);
+int arcvae_dec_chain_expect(const float* dense_logits, const float* lse, const float* cost, int n_cost, float* totals, float* visits,
+                            float* open_mass, int B, int V, int max_len, int end_token, float temperature, arcvae_stream_t stream);
 /* Exact K-best decoding: the K most probable admissible sequences per batch row of the same chain, by a list-Viterbi recursion.
  * The admissible sequences and the limits are those of arcvae_dec_viterbi.
  * Lists: a_t[v] is a list of at most K scores, non-increasing; rank r has the back pointer (u, r').  a_0[v] = [fl(0 + lp(0, v))].

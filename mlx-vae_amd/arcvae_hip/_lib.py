@@ -95,6 +95,8 @@ SIGNATURES = {
     "arcvae_dec_viterbi_ws_bytes": [_i, _i, _i, _lp],
     "arcvae_dec_viterbi": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _f, _vp],
     "arcvae_dec_chain_marginals": [_vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
+    "arcvae_dec_row_costs": [_vp, _vp, _f, _vp, _vp, _f, _vp, _vp, _l, _i, _vp],
+    "arcvae_dec_chain_expect": [_vp, _vp, _vp, _i, _vp, _vp, _vp, _i, _i, _i, _i, _f, _vp],
     "arcvae_dec_kbest_ws_bytes": [_i, _i, _i, _i, _lp],
     "arcvae_dec_kbest": [_vp, _vp, _vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _f, _vp],
     "arcvae_dec_viterbi_norm": [_vp] * 10 + [_l, _i, _i, _i, _i, _i, _i, _f, _vp],

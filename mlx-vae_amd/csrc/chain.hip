@@ -16,6 +16,9 @@
 //   viterbi    back pointers go to the caller's scratch as bytes [B, max_len, V]; the back-trace stages them through LDS in
 //              chunks of CHAIN_TRACE_BYTES and one thread follows them.
 //   marginals  writes alive[b, t, :] every step.
+//   expect     the marginals kernel with a pack of extra arguments (ChainExpect): alive stays in registers and LDS, the columns'
+//              owners keep running sums over the steps, and one block reduction after the last step forms the expectations; the
+//              plain instantiation has an empty pack and none of that code.  No LDS is added.
 //   viterbi_norm   the same kernel with a pack of extra arguments (ChainNorm): the end column's owner divides e_t by the length's
 //              divisor and compares keys, and stores e_t to the profile where asked; the plain instantiation has an empty pack
 //              and none of that code.
@@ -27,6 +30,7 @@ namespace {
 constexpr int CHAIN_THREADS = 256;
 constexpr int CHAIN_STAGE_V = 96;           // largest V whose V x V table is staged (36 KB: three workgroups per CU; V 80: five)
 constexpr int CHAIN_TRACE_BYTES = 8192;     // back pointers staged per chunk of the back-trace (>= 32 steps at V 256)
+constexpr int CHAIN_MAX_COST = 4;           // per-state costs a launch of the expectations takes
 // LDS (floats): vector A [256] | vector B [256] | partial results [256] x 2 (Viterbi: value and argument; the sum uses 256) |
 // lse [256] | control [4] (int / float) | table, or the back-trace's chunk
 constexpr int CHAIN_OFF_B = 256, CHAIN_OFF_PV = 512, CHAIN_OFF_LSE = 1024, CHAIN_OFF_CTL = 1280,
@@ -276,10 +280,29 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_trace_kernel(const uint8_
 }
 
 // ---- forward recursion -------------------------------------------------------------------------------------------------------
-template <bool STAGED>
+// What the expectations add to the kernel's arguments (arcvae_dec_chain_expect): the per-state costs and the outputs, each NULL
+// where not asked for.
+struct ChainExpect {
+    const float* cost;         // [n_cost, B*V]
+    float* totals;             // [B, n_cost]
+    float* visits;             // [B, V] or NULL
+    float* open_mass;          // [B] or NULL
+    int n_cost;                // 0 .. CHAIN_MAX_COST
+    int B;
+};
+
+// ExpectArgs: empty (arcvae_dec_chain_marginals: alive[b, t, :] goes to memory every step) or one ChainExpect
+// (arcvae_dec_chain_expect: alive is NULL and nothing is written per step; column v's owner keeps visits[v] = the sum of
+// alive[t][v] over all steps and cont[v] = the same over the steps whose tokens are fed back, 0 .. max_len-2 and v != end_token,
+// each added in step order; after the last step the workgroup reduces open_mass and the cost totals in one fixed order:
+// a butterfly per wave, the four waves' results through the dead partial-result area, added in ascending wave order).
+template <bool STAGED, class... ExpectArgs>
 __global__ __launch_bounds__(CHAIN_THREADS) void chain_marginals_kernel(const float* __restrict__ logits,
                                                                         const float* __restrict__ lse, float* alive, int V, int S,
-                                                                        int P, int max_len, int end_token, float inv_temp) {
+                                                                        int P, int max_len, int end_token, float inv_temp,
+                                                                        ExpectArgs... expect_args) {
+    constexpr bool EXPECT = sizeof...(ExpectArgs) > 0;
+    const ChainExpect ea = table_optional<ChainExpect>(expect_args...);
     extern __shared__ __align__(16) float smem[];
     float* cur = smem;
     float* nxt = smem + CHAIN_OFF_B;
@@ -298,9 +321,16 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_marginals_kernel(const fl
     cur[tid] = 0.f;                                           // (the pads V .. V4-1 and the end token stay 0 in both vectors)
     nxt[tid] = 0.f;
     __syncthreads();
+    float vis = 0.f, cont = 0.f, last = 0.f;                  // (EXPECT) the owner's sums and its alive[max_len-1][v]
     if (owner) {
         const float s = chain_term<STAGED, true>(tab, x, ls, 0, v, V, inv_temp);
-        ob[v] = s;
+        if (EXPECT) {
+            vis = s;
+            last = s;
+            if (v != end_token && max_len > 1) cont = s;
+        } else {
+            ob[v] = s;
+        }
         if (v != end_token) cur[v] = s;
     }
     __syncthreads();
@@ -319,13 +349,49 @@ __global__ __launch_bounds__(CHAIN_THREADS) void chain_marginals_kernel(const fl
         if (P > 1) __syncthreads();
         if (owner) {
             for (int q = 1; q < P; ++q) acc += pv[q * V + v];
-            ob[(long)t * V + v] = acc;
+            if (EXPECT) {
+                vis += acc;
+                last = acc;
+                if (v != end_token && t + 1 < max_len) cont += acc;
+            } else {
+                ob[(long)t * V + v] = acc;
+            }
             if (v != end_token) nxt[v] = acc;
         }
         __syncthreads();
         float* sw = cur;
         cur = nxt;
         nxt = sw;
+    }
+    if (EXPECT) {
+        // (the loop's last barrier is behind every read of the partial results: the area is dead)
+        if (owner && ea.visits) ea.visits[(long)b * V + v] = vis;
+        float part[CHAIN_MAX_COST + 1];                       // open_mass, then the totals: every thread takes part, with 0
+        part[0] = owner && v != end_token ? last : 0.f;
+#pragma unroll
+        for (int k = 0; k < CHAIN_MAX_COST; ++k) {
+            float r = 0.f;
+            // a state that is never fed back costs nothing, whatever its cost holds (0 * inf is not relied on)
+            if (k < ea.n_cost && owner && cont > 0.f) r = ea.cost[((long)k * ea.B + b) * V + v] * cont;
+            part[k + 1] = r;
+        }
+#pragma unroll
+        for (int k = 0; k <= CHAIN_MAX_COST; ++k) {
+            if (k > ea.n_cost) break;                         // (uniform)
+            const float w = wave_sum(part[k]);
+            if ((tid & 63) == 0) pv[(tid >> 6) * (CHAIN_MAX_COST + 1) + k] = w;
+        }
+        __syncthreads();
+        if (tid <= ea.n_cost) {
+            float s = pv[tid];
+            for (int w = 1; w < CHAIN_THREADS / 64; ++w) s += pv[w * (CHAIN_MAX_COST + 1) + tid];
+            if (tid == 0) {
+                if (ea.open_mass) ea.open_mass[b] = s;
+            } else {
+                const int k = tid - 1;
+                ea.totals[(long)b * ea.n_cost + k] = ea.cost[((long)k * ea.B + b) * V] + s;      // the start row always counts
+            }
+        }
     }
 }
 
@@ -400,5 +466,24 @@ extern "C" int arcvae_dec_chain_marginals(const float* dense_logits, const float
     else
         hipLaunchKernelGGL(chain_marginals_kernel<false>, dim3(B), dim3(CHAIN_THREADS), pl.lds, stream, dense_logits, lse, alive, V,
                            pl.S, pl.P, max_len, end_token, inv_temp);
+    return arcvae_launch_status();
+}
+
+extern "C" int arcvae_dec_chain_expect(const float* dense_logits, const float* lse, const float* cost, int n_cost, float* totals,
+                                       float* visits, float* open_mass, int B, int V, int max_len, int end_token,
+                                       float temperature, hipStream_t stream) {
+    if (!chain_args_ok(dense_logits, lse, B, V, max_len, end_token, temperature)) return ARCVAE_ERR_ARG;
+    if (n_cost < 0 || n_cost > CHAIN_MAX_COST || (cost != nullptr) != (n_cost > 0) || (totals != nullptr) != (n_cost > 0))
+        return ARCVAE_ERR_ARG;
+    if (n_cost == 0 && !visits && !open_mass) return ARCVAE_ERR_ARG;
+    const ChainPlan pl = chain_plan(V, false);
+    const float inv_temp = 1.0f / temperature;
+    const ChainExpect ea = {cost, totals, visits, open_mass, n_cost, B};
+    if (pl.staged)
+        hipLaunchKernelGGL((chain_marginals_kernel<true, ChainExpect>), dim3(B), dim3(CHAIN_THREADS), pl.lds, stream, dense_logits,
+                           lse, (float*)nullptr, V, pl.S, pl.P, max_len, end_token, inv_temp, ea);
+    else
+        hipLaunchKernelGGL((chain_marginals_kernel<false, ChainExpect>), dim3(B), dim3(CHAIN_THREADS), pl.lds, stream, dense_logits,
+                           lse, (float*)nullptr, V, pl.S, pl.P, max_len, end_token, inv_temp, ea);
     return arcvae_launch_status();
 }

@@ -68,7 +68,7 @@ static inline bool table_vocab_ok(int V) { return V >= 1 && V <= TABLE_MAX_V; }
 static inline bool table_dims_ok(int B, int V, int K, int max_len) {
     return B > 0 && table_vocab_ok(V) && K >= 1 && K <= TABLE_MAX_K && max_len >= 1;
 }
-// finite: chain.hip and kbest.hip refuse +inf; beam, swor, top-k/p and the table's own functions take it (inv_temp = 0: every
+// finite: chain.hip, kbest.hip and the row costs refuse +inf; beam, swor, top-k/p and the table's own functions take it (inv_temp = 0: every
 // row uniform).  A NaN fails either way.
 static inline bool table_temp_ok(float temperature, bool finite) {
     return temperature > 0.f && (!finite || temperature <= 3.402823466e+38f);

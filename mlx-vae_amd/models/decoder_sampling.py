@@ -12,7 +12,10 @@ sampling the reference marks TODO (decoder_sampling.py:115-116): an extension wi
 dense table defines (csrc/chain.hip); and `generate_kbest`: the exact K most probable sequences of that chain (csrc/kbest.hip);
 and `length_penalty=` on both (the exact optimum of the length-normalised score), `best_by_length` (the best score of every
 length) and `generate_of_length` (the most probable sequence of a given length); and `generate_without_replacement`: K distinct
-random sequences per row, exactly a sample without replacement, with `importance_weights` for unbiased estimates (csrc/swor.hip).
+random sequences per row, exactly a sample without replacement, with `importance_weights` for unbiased estimates (csrc/swor.hip);
+and `sequence_entropy` / `sequence_divergence` / `expected_token_counts` / `expected_length`: the exact entropy, cross-entropy
+and KL of the distribution over whole sequences and its expected token counts and length, closed forms on the forward recursion
+(csrc/table.hip row costs, csrc/chain.hip expectations; `_expect` is their one path).
 
 Every method is its argument checks, the decoder's one path to the table -- `load_conditions`, `dense_table`, `table_lse`,
 `scratch` (models/decoder.py) -- and its own kernel.  What the methods share beyond that is written once below: `_state` +
@@ -406,6 +409,91 @@ class MLXAutoregressiveDecoderSampling:
         last = alive[:, -1, :]
         rest = last.sum(dim=1) - last[:, self.end_token]
         return torch.cat([alive[:, :, self.end_token], rest[:, None]], dim=1)
+
+    def _expect(self, conditions, max_length, temperature, q=None, costs: bool = True, visits: bool = False):
+        """The one path of the exact expectations -> (totals [B, n_cost] or None, visits [B, V] or None): the dense pass,
+        arcvae_dec_row_lse, arcvae_dec_row_costs and arcvae_dec_chain_expect (include/arcvae_hip.h).  q = None: the row entropies
+        alone (n_cost 1); q = (other_conditions, other, other_temperature), each None where Q does not differ from P there: the
+        row cross-entropies against Q's table as well (n_cost 2).  The decoder's workspace is kept per (B, T), so a second dense
+        pass on the same decoder overwrites ws.logits: P's table is then held in a copy of B * V * V * 4 bytes."""
+        T, V, dev = int(max_length), self.decoder.vocab_size, self.decoder.store.device
+        self._check_chain(T, temperature)
+        if q is not None:
+            other_conditions, other, other_temperature = q
+            other = self if other is None else other
+            temperature_q = temperature if other_temperature is None else other_temperature
+            if not isinstance(other, MLXAutoregressiveDecoderSampling):
+                raise ValueError("other must be a MLXAutoregressiveDecoderSampling")
+            if other.decoder.vocab_size != V or other.end_token != self.end_token:
+                raise ValueError("other must have the same vocab_size and end_token")
+            other._check_chain(T, temperature_q)
+            if other_conditions is not None and len(other_conditions) != len(conditions):
+                raise ValueError("other_conditions must have one row per row of conditions")
+        ws, lse, B = self._table(conditions, T, temperature)
+        logits = ws.logits
+        cost = totals = counts = None
+        n_cost = 0
+        if costs and q is None:
+            n_cost = 1
+            cost = torch.empty(1, B * V, dtype=torch.float32, device=dev)
+            call("arcvae_dec_row_costs", ptr(logits), ptr(lse), float(temperature), None, None, float(temperature), ptr(cost),
+                 None, B * V, V, stream_ptr())
+        elif costs:
+            n_cost = 2
+            cost = torch.empty(2, B * V, dtype=torch.float32, device=dev)
+            if other_conditions is None and other.decoder is self.decoder:      # the same table, at most another temperature
+                logits_q = logits
+                lse_q = lse if float(temperature_q) == float(temperature) else self.decoder.table_lse(ws, temperature_q)
+            else:
+                if other.decoder is self.decoder:
+                    logits = logits.clone()                                      # (the second pass overwrites ws.logits)
+                ws_q, lse_q, _ = other._table(conditions if other_conditions is None else other_conditions, T, temperature_q)
+                logits_q = ws_q.logits
+            call("arcvae_dec_row_costs", ptr(logits), ptr(lse), float(temperature), ptr(logits_q), ptr(lse_q), float(temperature_q),
+                 ptr(cost[0]), ptr(cost[1]), B * V, V, stream_ptr())
+        if n_cost:
+            totals = torch.empty(B, n_cost, dtype=torch.float32, device=dev)
+        if visits:
+            counts = torch.empty(B, V, dtype=torch.float32, device=dev)
+        call("arcvae_dec_chain_expect", ptr(logits), ptr(lse), ptr(cost), n_cost, ptr(totals), ptr(counts), None, B, V, T,
+             self.end_token, float(temperature), stream_ptr())
+        return totals, counts
+
+    def sequence_entropy(self, conditions, max_length: int = 80, temperature: float = 1.0) -> torch.Tensor:
+        """Extension (absent in the reference): [B] float32, the entropy in nats of the distribution over whole molecules that
+        sample=True draws from at this temperature -- over the OUTCOMES of a row: a sequence up to and including its first
+        end_token, or max_length tokens without one.  Exact up to fp32 rounding, nothing is sampled: by the chain rule it is the
+        expected sum of the fed states' row entropies, a closed form on the forward recursion of token_marginals
+        (include/arcvae_hip.h arcvae_dec_row_costs, arcvae_dec_chain_expect)."""
+        totals, _ = self._expect(conditions, max_length, temperature)
+        return totals[:, 0].contiguous()
+
+    def expected_token_counts(self, conditions, max_length: int = 80, temperature: float = 1.0) -> torch.Tensor:
+        """Extension (absent in the reference): [B, V] float32, entry [b, v] = the expected number of times token v is emitted
+        in an outcome (token_marginals summed over the steps, without writing it).  Column end_token = P(the molecule ends
+        within max_length)."""
+        _, counts = self._expect(conditions, max_length, temperature, costs=False, visits=True)
+        return counts
+
+    def expected_length(self, conditions, max_length: int = 80, temperature: float = 1.0) -> torch.Tensor:
+        """Extension (absent in the reference): [B] float32, the expected number of tokens of an outcome, the end_token counted
+        and an outcome without one counting max_length: expected_token_counts summed over the tokens."""
+        return self.expected_token_counts(conditions, max_length, temperature).sum(dim=1)
+
+    def sequence_divergence(self, conditions, other_conditions=None, other=None, other_temperature=None, max_length: int = 80,
+                            temperature: float = 1.0):
+        """Extension (absent in the reference): (kl, cross_entropy, entropy), each [B] float32 in nats, between the outcome
+        distribution P of (self, conditions, temperature) and a second one Q, paired row by row and both cut at max_length:
+        entropy = sequence_entropy, cross_entropy = -E_P[log Q], kl = KL(P || Q) = cross_entropy - entropy, exactly (up to fp32
+        rounding; nothing is sampled).  Q differs from P in any of: its conditions (other_conditions, as many rows), its
+        temperature (other_temperature), its sampler (other: another MLXAutoregressiveDecoderSampling with the same vocab_size and
+        end_token, e.g. one loaded with load_from_decoder(decoder, ema=...)); None = as P.  With nothing given Q = P and kl is
+        exactly 0.  kl is not clamped: rounding may leave it slightly negative where P and Q nearly agree.  A token P emits and Q
+        cannot gives +inf.  Cost: a second dense pass where the conditions or the sampler differ, and, when that pass runs on
+        this sampler's own decoder, a copy of P's table, B * V * V * 4 bytes."""
+        totals, _ = self._expect(conditions, max_length, temperature, q=(other_conditions, other, other_temperature))
+        entropy, cross = totals[:, 0].contiguous(), totals[:, 1].contiguous()
+        return cross - entropy, cross, entropy
 
 
 def importance_weights(log_probs: torch.Tensor, threshold: torch.Tensor) -> torch.Tensor:
