@@ -1530,6 +1530,7 @@ struct PersistArgs {
     unsigned long long* trace;               // or null: {start, end} per tick of block (xcc 0, role 0)
     int B, T, H, V, RX, prio;
     int stagger;                             // two-group form: group 1 starts this many 10 ns units late (see ps_stagger)
+    int roles;                               // layer-split form: 0 = a tick's gate / cell stores ahead of its flag, 1 = behind it
 };
 
 // Two blocks of a CU that run the same tick loop fall into lockstep: both reach their matrix work together (and halve each
@@ -1607,6 +1608,12 @@ __device__ __forceinline__ void ps_take_role(unsigned* cnt, unsigned* cucnt, uns
 // wave sets after its LDS writes (release); only the epilogue wave of a layer stores exchanged h, drains its stores and
 // then publishes its flag (the one-lane flag row of the hand-off table: sc1 poll, the other waves load behind the LDS word
 // the polling wave sets).  A wave that gives up clears s_ok and raises PS_ERR; every spin checks both and is bounded.
+// Only h (and comb at the last tick) has to be in L2 before the flag: with PersistArgs::roles != 0 (ARCVAE_LS_ROLES, the
+// default) the epilogue wave stores h, drains, publishes the flag and only then issues the tick's four gate stores and its
+// cell store, which nothing reads before the launch ends -- five store issues and their acknowledgements off the chain of
+// both layers.  roles == 0 keeps all six stores ahead of the flag.  Epilogue wave kw 0 and polling wave kw 1 in both
+// layers, every wave at the step priority: moving layer 1's roles to kw 2 / 3 (one special role per SIMD) and putting layer
+// 1 above layer 0 (static, or only over layer 0's off-chain section) were measured and lost (DESIGN_HISTORY.md).
 constexpr int PS_LS_FLAGS = 1024;   // layer-1 flag lines of the layer-split forward ([8 XCDs][32]; the two-group form's words:
                                     // never used by the same shape), inside what arcvae_enc_prologue re-arms
 constexpr int PS_LS_RD = 2;         // ring slots of Wx1 h0 accumulators (16 KB each)
@@ -1627,7 +1634,9 @@ __device__ void lstm_fwd_persist_split(const PersistArgs& a) {
     __shared__ unsigned s_role, s_xcc;
     __shared__ int s_ok;
     arcvae_set_prio(a.prio);
-    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, ly = wave >> 2, kw = wave & 3;
+    // wave, ly, kw in SGPRs (readfirstlane): every branch on a wave's role is a scalar branch, not an EXEC mask
+    const int tid = threadIdx.x, lane = tid & 63, wave = __builtin_amdgcn_readfirstlane(tid >> 6), ly = wave >> 2, kw = wave & 3;
+    const bool late = a.roles != 0;                  // the gate / cell stores of a tick behind its flag (ARCVAE_LS_ROLES)
     const int B = a.B, T = a.T;
     if (tid == 0) {
         s_xcc = ps_xcc_id();
@@ -1670,8 +1679,16 @@ __device__ void lstm_fwd_persist_split(const PersistArgs& a) {
     const int erow = lane >> 3, ul = lane & 7, eb = row0 + erow, unit = role * UW + ul;
     const bool eact = kw == 0 && erow < RX && eb < B;
     const bool tr = a.trace && xcc == 0 && role == 0 && kw == 0 && lane == 0;
-#ifdef ARCVAE_PS_STAMPS   // diagnostic build: four stamps per tick and chain at trace[8 t + 4 ly + k]
-#define LS_STAMP(k) do { if (tr) a.trace[8 * (long)t + 4 * ly + (k)] = wall_clock64(); } while (0)
+#ifdef ARCVAE_PS_STAMPS   // diagnostic build: five stamps per tick, chain and stamped wave (w = 0 epilogue wave, 1 polling wave) at
+                          // trace[32 t + 16 ly + 8 w + k]; behind the T + 1 tick rows, HW_ID of the block's eight waves
+    const bool trs = a.trace && xcc == 0 && role == 0 && (kw == 0 || kw == 1) && lane == 0;
+    const int trb = 16 * ly + (kw == 1 ? 8 : 0);
+    if (a.trace && xcc == 0 && role == 0 && lane == 0) {
+        unsigned hwid;
+        asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hwid));
+        a.trace[32 * (long)(T + 1) + wave] = hwid;
+    }
+#define LS_STAMP(k) do { if (trs) a.trace[32 * (long)t + trb + (k)] = wall_clock64(); } while (0)
 #else
 #define LS_STAMP(k) do { } while (0)
 #endif
@@ -1701,6 +1718,9 @@ __device__ void lstm_fwd_persist_split(const PersistArgs& a) {
                 }
                 __builtin_amdgcn_s_sleep(1);
             }
+#ifdef ARCVAE_PS_STAMPS
+            if (trs) a.trace[32 * (long)t + trb + 5] = spins;
+#endif
             if (lane == 0) ls_st(cw + ly, (unsigned)t);
             return true;
         }
@@ -1720,6 +1740,12 @@ __device__ void lstm_fwd_persist_split(const PersistArgs& a) {
     // the epilogue of my layer's tick t (wave 0 of the layer): gates from the four waves' partials, c in a register
     float cst = 0.f;
     auto epilogue = [&](int t, const float (&pv)[4]) {
+        float gi = 0.f, gf = 0.f, gg = 0.f, go = 0.f, c = 0.f;
+        auto store_gc = [&]() {                                  // gate and cell sequences: read only after the launch
+            float* gp = a.gseq + ly * lG + (long)t * sG + (long)eb * G + unit;
+            gp[0] = gi; gp[H] = gf; gp[2 * H] = gg; gp[3 * H] = go;
+            a.cseq[ly * lH + (long)t * sH + (long)eb * H + unit] = c;
+        };
         if (eact) {
             const int cb = erow * CW + 16 * (ul >> 2) + (ul & 3);
             const float* rl = red + ly * 1024;
@@ -1729,22 +1755,21 @@ __device__ void lstm_fwd_persist_split(const PersistArgs& a) {
                 const int o = cb + 4 * g;
                 v[g] = (rl[o] + rl[256 + o]) + (rl[512 + o] + rl[768 + o]);
             }
-            const float gi = chain_sigmoid(v[0] + pv[0]);
-            const float gf = chain_sigmoid(v[1] + pv[1]);
-            const float gg = chain_tanh(v[2] + pv[2]);
-            const float go = chain_sigmoid(v[3] + pv[3]);
-            const float c = t > 0 ? gf * cst + gi * gg : gi * gg;   // MLX: cell=None at t == 0 -> c = i*g
+            gi = chain_sigmoid(v[0] + pv[0]);
+            gf = chain_sigmoid(v[1] + pv[1]);
+            gg = chain_tanh(v[2] + pv[2]);
+            go = chain_sigmoid(v[3] + pv[3]);
+            c = t > 0 ? gf * cst + gi * gg : gi * gg;            // MLX: cell=None at t == 0 -> c = i*g
             cst = c;
             const long hb = (long)eb * H + unit;
             const float hval = go * chain_tanh(c);
             a.hseq[ly * lH + (long)t * sH + hb] = hval;
             if (a.comb && ly == 1 && t == T - 1) a.comb[(long)eb * 2 * H + unit] = hval;
-            float* gp = a.gseq + ly * lG + (long)t * sG + (long)eb * G + unit;
-            gp[0] = gi; gp[H] = gf; gp[2 * H] = gg; gp[3 * H] = go;
-            a.cseq[ly * lH + (long)t * sH + hb] = c;
+            if (!late) store_gc();
         }
         ps_stores_in_l2();                                       // my h stores have reached the XCD's L2
         if (lane == 0) __hip_atomic_store(my_flag, (unsigned)(t + 1), __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
+        if (late && eact) store_gc();
     };
     // my quarter's partial of the tick -> red, then count it (the LDS writes complete before the release)
     auto put_partial = [&](const f32x4 (&acc)[4]) {
@@ -1789,11 +1814,12 @@ __device__ void lstm_fwd_persist_split(const PersistArgs& a) {
 #ifndef ARCVAE_PS_STAMPS
                     if (tr && t == 0) a.trace[1] = wall_clock64();
 #endif
-                }
+                } else { LS_STAMP(2); LS_STAMP(3); }     // (the polling wave's row: partial counted)
             }
             if (t > 0) {                                 // off the chain: Wx1 h0_{t-1} -> ring slot (t-1) % RD
                 const int j = t - 1;
                 if (j >= RD && !lds_wait(cw + 8 + kw, (unsigned)(j - RD + 1))) return;
+                LS_STAMP(4);
                 f32x4 acc[4];
 #pragma unroll
                 for (int e = 0; e < 4; ++e) acc[e] = f32x4{0.f, 0.f, 0.f, 0.f};
@@ -1818,6 +1844,7 @@ __device__ void lstm_fwd_persist_split(const PersistArgs& a) {
                 qh[1] = ps_load_sc1_x4(rs, qoff + 128);
             }
             if (!lds_wait(cw + 4 + kw, (unsigned)(t + 1))) return;   // ring slot t: my quarter's Wx1 h0_t accumulators
+            LS_STAMP(4);
             f32x4 acc[4];
             const f32x4* rs = ring + ((t % RD) * 4 + kw) * 256 + lane;
 #pragma unroll
@@ -1833,7 +1860,7 @@ __device__ void lstm_fwd_persist_split(const PersistArgs& a) {
 #ifndef ARCVAE_PS_STAMPS
                 if (tr) a.trace[2 * (t + 1) + 1] = wall_clock64();
 #endif
-            }
+            } else { LS_STAMP(2); LS_STAMP(3); }
         }
     }
 #undef LS_WLDS
@@ -2223,6 +2250,10 @@ inline bool persist_layer_split(int B, int H, int L) {
     return arcvae_env_int("ARCVAE_LAYER_SPLIT", 1) != 0 && arcvae_env_int("ARCVAE_FWD_MFMA", 1) != 0 && H == 256 && L == 2
            && ceil_div(B, 8) <= 8;
 }
+// The layer-split forward's form (ARCVAE_LS_ROLES, read at every call): 0 = the parent form (every store of a tick ahead of
+// its flag), 1 (default) = the form kept from the role / priority / store-order measurements (lstm_fwd_persist_split: the
+// gate and cell stores behind the flag; any non-zero value, as for ARCVAE_LAYER_SPLIT).
+inline int persist_ls_roles() { return arcvae_env_int("ARCVAE_LS_ROLES", 1) != 0 ? 1 : 0; }
 // LDS allocation floor of the register-stationary persistent kernels (ARCVAE_PERSIST_LDS_KB, default 81 = more than half
 // of a CU's 160 KB): two of their blocks can then never share a CU, whatever else is resident.
 inline size_t persist_lds_floor() { return (size_t)arcvae_env_int("ARCVAE_PERSIST_LDS_KB", 81) * 1024; }
@@ -3327,6 +3358,7 @@ extern "C" int arcvae_enc_lstm_forward_persistent(const int32_t* x_tb, const flo
     a.sync = sync_ws; a.start_signal = start_signal; a.trace = trace;
     a.flags = sync_ws + PS_FLAGS; a.cnt = sync_ws + PS_CNT; a.cucnt = nullptr; a.stagger = 0;
     a.B = B; a.T = T; a.H = H; a.V = V; a.RX = ceil_div(B, 8); a.prio = arcvae_step_prio();
+    a.roles = persist_ls_roles();
     if (persist_two_groups(B, H, L, 1)) {   // two blocks per CU, two independent 16-row recurrences per XCD (the caller's
         if (!(flags & 1)) {              // re-arm covers PS2_WORDS: arcvae_enc_prologue, or here)
             rc = arcvae_zero(reinterpret_cast<float*>(sync_ws + PS2_FWD_FLAGS), 1, PS2_WORDS - PS2_FWD_FLAGS, PS2_WORDS - PS2_FWD_FLAGS, stream);

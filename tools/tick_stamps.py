@@ -9,6 +9,7 @@ import os, sys
 import numpy as np
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
 os.environ.setdefault("ARCVAE_HIP_LIB", os.path.join(ROOT, "ab_libs", "libarcvae_stamps.so"))   # the diagnostic build
+os.environ["ARCVAE_LAYER_SPLIT"] = "0"   # these are the one-chain form's stamps (the layer-split form's, wider rows: tick_stamps_layers.py)
 for p in ("mlx-vae_amd", "tests", "oracle"): sys.path.insert(0, os.path.join(ROOT, p))
 import torch
 import arcvae_hip.engine as E
