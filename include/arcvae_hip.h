@@ -541,6 +541,38 @@ int arcvae_dec_topkp_ws_bytes(int B, int V, int top_k, long* bytes);
 int arcvae_dec_sample_chain_topkp(const float* dense_logits, int32_t* tokens, int32_t* first_end, void* ws, long ws_bytes, int B,
                                   int V, int max_len, int end_token, float temperature, int top_k, float top_p,
                                   const unsigned long long* seed, arcvae_stream_t stream);
+/* Min-p, locally typical and minimum-length truncated sampling: further rules that write the lists the top-k / top-p walk reads.
+ * Beyond the top-k / top-p limits: 0 <= min_p < 1 (0 = off); 0 < typical_p <= 1 (1 = off); typical_p < 1 requires top_p == 1 and
+ * min_p == 0; 0 <= min_len <= max_len; min_len > 0 requires 0 <= end_token < V and V >= 2; ban_token is -1 (none) or in [0, V),
+ * and a ban_token >= 0 requires V >= 2.
+ * s, the order, K, e_i = expf(fl(s_i - s_0)), C and M_K as above, with one change: a banned token sorts behind every real token
+ *   (the value part of its key is 0, like the padding beyond V; its index part is kept) and |K| = min(top_k or V, V - 1).
+ * The s-descending family (typical_p == 1): the nucleus rule as above gives n_p; min-p keeps position i >= 1 of K iff
+ *   e_i >= min_p (e_0 = 1 is the image of the row's largest probability, so e_i = p_i / p_max: renormalisation does not enter),
+ *   n_m = the first position that fails (|K| if none); n = min(n_p, n_m).  With min_p = 0 and no banned token the rows and the
+ *   walk are arcvae_dec_topkp_rows' / arcvae_dec_sample_chain_topkp's, bit for bit.
+ * The typical family (typical_p < 1; Meister et al. 2022), over the same K in the same s-order: a_i = fl(s_i - s_0),
+ *   l_i = fl(a_i - logf(M_K)) -- the log of the renormalised probability, from s and not from e, so finite where e_i underflows;
+ *   H = fl(-(sum over K of fl(e_i * l_i)) / M_K), the fp32 sum in the kernel's own, fixed order; d_i = |fl(l_i + H)|.  Typical
+ *   order: position i precedes i' iff d_i < d_i', or d_i == d_i' and i < i' (ties to the higher s, then the lower token).  e'_q, C'_q =
+ *   the masses in that order and their fp32 inclusive prefix sums, M' = C'_{|K|-1}; position q is kept iff q == 0 or
+ *   fl(C'_q - e'_q) < fl(typical_p * M'); n = the first position that fails (|K| if none).  A prefix rule, as the nucleus:
+ *   the warper of HuggingFace transformers keeps the tokens that tie at the cut instead.
+ * arcvae_dec_trunc_rows: as arcvae_dec_topkp_rows.  Typical family: tokens[i, :] = the typical order over K, then the rest of the
+ *   s-order (a banned token last); cum = C'; dev [R, V] (NULL allowed): dev[i, q] = d of position q < |K|, 0 beyond; ent [R] (NULL
+ *   allowed) = H.  The other family writes dev and ent as 0 where asked for.
+ * arcvae_dec_sample_chain_trunc: the walk of arcvae_dec_sample_chain_topkp (same generator, theta and pick rule), where a step
+ *   t < min_len reads the lists built with ban_token = end_token and a step t >= min_len the plain ones: no end token appears
+ *   before position min_len.  This is the LOCAL mask of the usual minimum-length processor, not conditioning on a length >=
+ *   min_len: it changes the measure that is sampled (a prefix keeps the probability it had, the end token's mass is shared out
+ *   among the other tokens of its step).  ws: 1 + (min_len > 0) list sets of the top-k / top-p size. */
+int arcvae_dec_trunc_rows(const float* dense_logits, long table_rows, const int32_t* rows, long R, int V, float temperature,
+                          int top_k, float top_p, float min_p, float typical_p, int ban_token, int32_t* count, int32_t* tokens,
+                          float* cum, float* dev, float* ent, arcvae_stream_t stream);
+int arcvae_dec_trunc_ws_bytes(int B, int V, int top_k, int min_len, long* bytes);
+int arcvae_dec_sample_chain_trunc(const float* dense_logits, int32_t* tokens, int32_t* first_end, void* ws, long ws_bytes, int B,
+                                  int V, int max_len, int min_len, int end_token, float temperature, int top_k, float top_p,
+                                  float min_p, float typical_p, const unsigned long long* seed, arcvae_stream_t stream);
 /* Sampling WITHOUT replacement: K distinct sequences per batch row that are exactly a sample without replacement from the sequence
  * distribution arcvae_dec_sample_chain_categorical draws from (stochastic beam search: Kool, van Hoof and Welling, ICML 2019).
  * ws: the back pointers.  arcvae_dec_swor, per batch row b:

@@ -16,6 +16,9 @@
 // 80 / 128, V 80) against 0.23 / 0.27 ms for pre-pass + walk: one wave per SIMD has nothing to hide the sort's latency
 // (DESIGN.md section 10).  The pre-pass and the materialising entry point run the same topkp_row, so the walk's decisions are
 // those of the inspected rows, bit for bit.
+// Min-p, locally typical and minimum-length sampling (arcvae_dec_trunc_rows / arcvae_dec_sample_chain_trunc; restated by
+// tests/trunc_ref.py) write the same lists by other rules (trunc_row) and walk them with the same kernel: min_len > 0 is a second
+// list set, built with the end token banned, which the steps t < min_len read.
 #include "table.h"
 
 namespace {
@@ -135,27 +138,42 @@ __global__ __launch_bounds__(256) void topkp_rows_kernel(const float* __restrict
 }
 
 // ---- the walk over the pre-pass lists: one wave per batch row, the seed read from device memory (one captured graph serves
-// every seed).  A step issues its row's count and lists together: one dependent round of loads per step -------------------------
+// every seed).  A step issues its row's count and lists together: one dependent round of loads per step.
+// MinLenArgs: empty (the top-k / top-p walk) or one WalkMinLen (arcvae_dec_sample_chain_trunc with min_len > 0): the lists a step
+// t < min_len reads instead, built with the end token banned ------------------------------------------------------------------
+struct WalkMinLen {
+    const int32_t* count;
+    const float* cum;
+    const uint8_t* tok;
+    int min_len;
+};
+
+template <class... MinLenArgs>
 __global__ __launch_bounds__(256) void topkp_walk_kernel(const int32_t* __restrict__ count, const float* __restrict__ cum,
                                                          const uint8_t* __restrict__ tok, int32_t* tokens, int32_t* first_end,
                                                          int B, int V, int S, int max_len, int end_token,
-                                                         const unsigned long long* __restrict__ seed_ptr) {
+                                                         const unsigned long long* __restrict__ seed_ptr, MinLenArgs... min_len_args) {
     const int lane = threadIdx.x & 63, b = blockIdx.x * 4 + (threadIdx.x >> 6);
     if (b >= B) return;                                   // wave-uniform
+    const WalkMinLen ml = table_optional<WalkMinLen>(min_len_args...);
     const unsigned long long seed = *seed_ptr;
     const unsigned long long key0 = table_row_key(seed, b);
     int cur = 0, fe = max_len;
     for (int t = 0; t < max_len; ++t) {
         const long r = (long)b * V + cur;
+        const bool banned = sizeof...(MinLenArgs) > 0 && t < ml.min_len;          // (false at compile time without the pack)
+        const int32_t* __restrict__ count_t = banned ? ml.count : count;
+        const float* __restrict__ cum_t = banned ? ml.cum : cum;
+        const uint8_t* __restrict__ tok_t = banned ? ml.tok : tok;
         float cm[4];
         int tk[4];
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const int p = 4 * lane + e;
-            cm[e] = p < S ? cum[r * S + p] : 0.f;
-            tk[e] = p < S ? (int)tok[r * S + p] : 0;
+            cm[e] = p < S ? cum_t[r * S + p] : 0.f;
+            tk[e] = p < S ? (int)tok_t[r * S + p] : 0;
         }
-        const int n = min(max(count[r], 1), S);
+        const int n = min(max(count_t[r], 1), S);
         const float c_last = __shfl(topkp_pick4(cm, (n - 1) & 3), (n - 1) >> 2, 64);
         const unsigned long long rnd = mix64(key0 + (unsigned long long)t);
         const float theta = (float)table_u24(rnd) * (1.0f / 16777216.0f) * c_last;   // 24 uniform bits in [0, 1), times C_{n-1}
@@ -172,6 +190,169 @@ __global__ __launch_bounds__(256) void topkp_walk_kernel(const int32_t* __restri
     if (lane == 0) first_end[b] = fe;
 }
 
+// ---- min-p, locally typical and banned-token truncation (arcvae_dec_trunc_rows / arcvae_dec_sample_chain_trunc): another way to
+// write the same lists.  trunc_row<false> is topkp_row with a banned token (the value part of its key is 0: it sorts behind
+// every real token, and |K| <= V - 1 keeps it out) and the min-p test on top of the nucleus test; with min_p = 0 and no ban its
+// operations are topkp_row's.  trunc_row<true> re-orders K by d = |log p + H| with a second sort and applies the prefix rule
+// in that order ------------------------------------------------------------------------------------------------------------------
+
+// C = the inclusive prefix sums of the wave's 256 masses in position order (in-lane, then across lanes), 0 from position K on:
+// the scan of topkp_row, operation for operation
+__device__ __forceinline__ void trunc_scan(const float (&ev)[4], int K, int lane, float (&cum)[4]) {
+    float c[4], run = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        run += ev[e];
+        c[e] = run;
+    }
+    float incl = run;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const float up = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += up;
+    }
+    float before = __shfl_up(incl, 1, 64);
+    if (lane == 0) before = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) cum[e] = 4 * lane + e < K ? before + c[e] : 0.f;
+}
+
+// n = the first position >= 1 of K that is not kept (|K| if every one is)
+__device__ __forceinline__ int trunc_count(const bool (&keep)[4], int K, int lane) {
+    int fail = TABLE_MAX_V;
+#pragma unroll
+    for (int e = 3; e >= 0; --e) {
+        const int p = 4 * lane + e;
+        if (p >= 1 && p < K && !keep[e]) fail = p;
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) fail = min(fail, __shfl_xor(fail, o, 64));
+    return min(fail, K);
+}
+
+// Outputs as topkp_row; dev = d of each position < |K| and ent = H (wave-uniform) in the typical family, 0 otherwise.
+template <bool TYPICAL>
+__device__ __forceinline__ void trunc_row(const float* __restrict__ row, int V, float inv_temp, int K, float top_p, float min_p,
+                                          float typical_p, int ban, int lane, int (&tok)[4], float (&cum)[4], float (&dev)[4], int& n,
+                                          float& ent) {
+    unsigned long long key[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int j = 4 * lane + e;
+        key[e] = 0ull;
+        if (j < V) {
+            float s = table_scaled(row[j], inv_temp);
+            if (s == 0.f) s = 0.f;                       // -0 folded into +0, as topkp_row
+            key[e] = (j == ban ? 0ull : (unsigned long long)ordered_key(s) << 8) | (unsigned long long)(255 - j);
+        }
+    }
+    topkp_sort(key, lane);
+    float a[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        tok[e] = 255 - (int)(key[e] & 255ull);
+        a[e] = ordered_value((unsigned)(key[e] >> 8));
+    }
+    const float m = __shfl(a[0], 0, 64);                  // position 0: the row's largest s
+    float ev[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        a[e] -= m;                                        // a_i = fl(s_i - s_0)
+        ev[e] = 4 * lane + e < K ? expf(a[e]) : 0.f;
+    }
+    trunc_scan(ev, K, lane, cum);
+    const float mk = __shfl(topkp_pick4(cum, (K - 1) & 3), (K - 1) >> 2, 64);   // M_K = C_{|K|-1}
+    bool keep[4];
+    if (!TYPICAL) {
+        const float thr = top_p * mk;
+#pragma unroll
+        for (int e = 0; e < 4; ++e) {
+            keep[e] = (top_p >= 1.f ? ev[e] > 0.f : cum[e] - ev[e] < thr) && ev[e] >= min_p;
+            dev[e] = 0.f;
+        }
+        ent = 0.f;
+        n = trunc_count(keep, K, lane);
+        return;
+    }
+    // H = -sum e_i * l_i / M_K with l_i = a_i - log M_K (from s, not from e: finite where e_i underflows); lanes in position order
+    // in the lane, then one xor butterfly (both partners add the same two numbers: every lane ends with the same bits)
+    const float logm = logf(mk);
+    float l[4], part = 0.f;
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        l[e] = a[e] - logm;
+        if (4 * lane + e < K && ev[e] > 0.f) part += ev[e] * l[e];
+    }
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) part += __shfl_xor(part, o, 64);
+    ent = -part / mk;
+    // the typical order: d ascending, then the s-position ascending; positions >= |K| keep their place behind K
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int p = 4 * lane + e;
+        const unsigned d_bits = __float_as_uint(fabsf(l[e] + ent));
+        key[e] = (p < K ? (unsigned long long)(0x7fffffffu - d_bits) << 16 : 0ull) | (unsigned long long)(255 - p) << 8 |
+                 (unsigned long long)tok[e];
+    }
+    topkp_sort(key, lane);
+    float em[4];
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int from = 255 - (int)((key[e] >> 8) & 255ull);              // this position's place in the s-order
+        tok[e] = (int)(key[e] & 255ull);
+        dev[e] = 4 * lane + e < K ? __uint_as_float(0x7fffffffu - (unsigned)(key[e] >> 16)) : 0.f;
+        float g[4];
+#pragma unroll
+        for (int i = 0; i < 4; ++i) g[i] = __shfl(ev[i], from >> 2, 64);
+        em[e] = topkp_pick4(g, from & 3);                 // e'_q; 0 from |K| on, where nothing moved
+    }
+    trunc_scan(em, K, lane, cum);
+    const float thr = typical_p * __shfl(topkp_pick4(cum, (K - 1) & 3), (K - 1) >> 2, 64);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) keep[e] = cum[e] - em[e] < thr;
+    n = trunc_count(keep, K, lane);
+}
+
+// One list set of the rows kernel: where it writes, its |K| and its banned token (-1 = none)
+struct TruncSet {
+    int32_t* count;
+    void* tokens;
+    float* cum;
+    int K;
+    int ban;
+};
+
+// As topkp_rows_kernel; S = the lists' row stride (|K| of the plain set in the pre-pass, V otherwise).  blockIdx.y picks the
+// list set: 0 the plain one, 1 (the pre-pass of a walk with min_len > 0) the one with the end token banned.
+template <bool PREPASS, bool TYPICAL>
+__global__ __launch_bounds__(256) void trunc_rows_kernel(const float* __restrict__ logits, long table_rows,
+                                                         const int32_t* __restrict__ rows, long R, int V, float inv_temp, int S,
+                                                         float top_p, float min_p, float typical_p, TruncSet plain, TruncSet banned,
+                                                         float* dev, float* ent) {
+    const int lane = threadIdx.x & 63;
+    const long i = (long)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (i >= R) return;                                   // wave-uniform
+    const TruncSet set = blockIdx.y ? banned : plain;
+    const long r = rows ? min(max((long)rows[i], 0L), table_rows - 1) : i;
+    int tk[4], n;
+    float cm[4], dv[4], h;
+    trunc_row<TYPICAL>(logits + r * V, V, inv_temp, set.K, top_p, min_p, typical_p, set.ban, lane, tk, cm, dv, n, h);
+#pragma unroll
+    for (int e = 0; e < 4; ++e) {
+        const int p = 4 * lane + e;
+        if (p < S) {
+            if (PREPASS) ((uint8_t*)set.tokens)[i * S + p] = (uint8_t)tk[e];
+            else ((int32_t*)set.tokens)[i * S + p] = tk[e];
+            set.cum[i * S + p] = cm[e];
+            if (!PREPASS && dev) dev[i * S + p] = dv[e];
+        }
+    }
+    if (lane == 0) {
+        set.count[i] = n;
+        if (!PREPASS && ent) ent[i] = h;
+    }
+}
+
 bool topkp_args_ok(int V, float temperature, int top_k, float top_p) {
     return table_vocab_ok(V) && table_temp_ok(temperature, false) && top_k >= 0 && top_p > 0.f && top_p <= 1.f;   // (NaN fails)
 }
@@ -183,6 +364,20 @@ long topkp_ws_bytes(int B, int V, int top_k) {
     const long R = (long)B * V, S = topkp_set_size(V, top_k);
     return R * 4 + R * S * 4 + R * S;
 }
+
+// min_p in [0, 1) (0 = off), typical_p in (0, 1] (1 = off); the typical family takes no nucleus and no min-p.  (A NaN fails.)
+bool trunc_args_ok(int V, float temperature, int top_k, float top_p, float min_p, float typical_p) {
+    return topkp_args_ok(V, temperature, top_k, top_p) && min_p >= 0.f && min_p < 1.f && typical_p > 0.f && typical_p <= 1.f &&
+           (typical_p >= 1.f || (top_p == 1.f && min_p == 0.f));
+}
+
+bool trunc_ban_ok(int ban, int V) { return ban == -1 || (ban >= 0 && ban < V && V >= 2); }
+
+// |K| = min(top_k or V, V - 1 with a banned token)
+int trunc_set_size(int V, int top_k, int ban) { return min(topkp_set_size(V, top_k), ban >= 0 ? V - 1 : V); }
+
+// one list set, or two with min_len > 0 (the second with the end token banned), each of the top-k / top-p size
+long trunc_ws_bytes(int B, int V, int top_k, int min_len) { return (min_len > 0 ? 2 : 1) * topkp_ws_bytes(B, V, top_k); }
 
 }  // namespace
 
@@ -216,7 +411,70 @@ extern "C" int arcvae_dec_sample_chain_topkp(const float* dense_logits, int32_t*
     uint8_t* tok = (uint8_t*)(cum + R * S);
     hipLaunchKernelGGL(topkp_rows_kernel<true>, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, stream, dense_logits, R,
                        (const int32_t*)nullptr, R, V, 1.0f / temperature, (int)S, top_p, count, (void*)tok, cum);
-    hipLaunchKernelGGL(topkp_walk_kernel, dim3(ceil_div(B, 4)), dim3(256), 0, stream, count, cum, tok, tokens, first_end, B, V,
+    hipLaunchKernelGGL(topkp_walk_kernel<>, dim3(ceil_div(B, 4)), dim3(256), 0, stream, count, cum, tok, tokens, first_end, B, V,
                        (int)S, max_len, end_token, seed);
+    return arcvae_launch_status();
+}
+
+extern "C" int arcvae_dec_trunc_rows(const float* dense_logits, long table_rows, const int32_t* rows, long R, int V,
+                                     float temperature, int top_k, float top_p, float min_p, float typical_p, int ban_token,
+                                     int32_t* count, int32_t* tokens, float* cum, float* dev, float* ent, hipStream_t stream) {
+    if (!dense_logits || !count || !tokens || !cum || table_rows <= 0 || R <= 0 ||
+        !trunc_args_ok(V, temperature, top_k, top_p, min_p, typical_p) || !trunc_ban_ok(ban_token, V))
+        return ARCVAE_ERR_ARG;
+    if ((!rows && R > table_rows) || (R + 3) / 4 > 0x7fffffffL) return ARCVAE_ERR_ARG;
+    const TruncSet set = {count, (void*)tokens, cum, trunc_set_size(V, top_k, ban_token), ban_token};
+    const dim3 grid((unsigned)((R + 3) / 4));
+    if (typical_p < 1.f)
+        hipLaunchKernelGGL((trunc_rows_kernel<false, true>), grid, dim3(256), 0, stream, dense_logits, table_rows, rows, R, V,
+                           1.0f / temperature, V, top_p, min_p, typical_p, set, set, dev, ent);
+    else
+        hipLaunchKernelGGL((trunc_rows_kernel<false, false>), grid, dim3(256), 0, stream, dense_logits, table_rows, rows, R, V,
+                           1.0f / temperature, V, top_p, min_p, typical_p, set, set, dev, ent);
+    return arcvae_launch_status();
+}
+
+extern "C" int arcvae_dec_trunc_ws_bytes(int B, int V, int top_k, int min_len, long* bytes) {
+    if (!bytes || B <= 0 || !table_vocab_ok(V) || top_k < 0 || min_len < 0) return ARCVAE_ERR_ARG;
+    *bytes = trunc_ws_bytes(B, V, top_k, min_len);
+    return ARCVAE_OK;
+}
+
+extern "C" int arcvae_dec_sample_chain_trunc(const float* dense_logits, int32_t* tokens, int32_t* first_end, void* ws, long ws_bytes,
+                                             int B, int V, int max_len, int min_len, int end_token, float temperature, int top_k,
+                                             float top_p, float min_p, float typical_p, const unsigned long long* seed,
+                                             hipStream_t stream) {
+    if (!dense_logits || !tokens || !first_end || !ws || !seed || B <= 0 || max_len <= 0 ||
+        !trunc_args_ok(V, temperature, top_k, top_p, min_p, typical_p) || !table_min_len_ok(min_len, max_len) ||
+        (min_len > 0 && (!table_end_ok(end_token, V) || V < 2)))
+        return ARCVAE_ERR_ARG;
+    if (ws_bytes < trunc_ws_bytes(B, V, top_k, min_len) || ((long)B * V + 3) / 4 > 0x7fffffffL) return ARCVAE_ERR_ARG;
+    const long R = (long)B * V, S = topkp_set_size(V, top_k), sets = min_len > 0 ? 2 : 1;
+    // list set 0: the plain lists; set 1 (min_len > 0 only): the lists with the end token banned.  The arrays of one kind lie
+    // together, count | cum | tok, so that every int32 and fp32 array stays 4-byte aligned whatever R * S is
+    TruncSet set[2];
+    for (long i = 0; i < sets; ++i) {
+        int32_t* count = (int32_t*)ws + i * R;
+        float* cum = (float*)((int32_t*)ws + sets * R) + i * R * S;
+        uint8_t* tok = (uint8_t*)((float*)((int32_t*)ws + sets * R) + sets * R * S) + i * R * S;
+        const int ban = i ? end_token : -1;
+        set[i] = {count, (void*)tok, cum, trunc_set_size(V, top_k, ban), ban};
+    }
+    if (sets == 1) set[1] = set[0];
+    const dim3 grid((unsigned)((R + 3) / 4), min_len > 0 ? 2 : 1);
+    if (typical_p < 1.f)
+        hipLaunchKernelGGL((trunc_rows_kernel<true, true>), grid, dim3(256), 0, stream, dense_logits, R, (const int32_t*)nullptr, R,
+                           V, 1.0f / temperature, (int)S, top_p, min_p, typical_p, set[0], set[1], (float*)nullptr, (float*)nullptr);
+    else
+        hipLaunchKernelGGL((trunc_rows_kernel<true, false>), grid, dim3(256), 0, stream, dense_logits, R, (const int32_t*)nullptr, R,
+                           V, 1.0f / temperature, (int)S, top_p, min_p, typical_p, set[0], set[1], (float*)nullptr, (float*)nullptr);
+    if (min_len > 0) {
+        const WalkMinLen ml = {set[1].count, set[1].cum, (const uint8_t*)set[1].tokens, min_len};
+        hipLaunchKernelGGL(topkp_walk_kernel<WalkMinLen>, dim3(ceil_div(B, 4)), dim3(256), 0, stream, set[0].count, set[0].cum,
+                           (const uint8_t*)set[0].tokens, tokens, first_end, B, V, (int)S, max_len, end_token, seed, ml);
+    } else {
+        hipLaunchKernelGGL(topkp_walk_kernel<>, dim3(ceil_div(B, 4)), dim3(256), 0, stream, set[0].count, set[0].cum,
+                           (const uint8_t*)set[0].tokens, tokens, first_end, B, V, (int)S, max_len, end_token, seed);
+    }
     return arcvae_launch_status();
 }

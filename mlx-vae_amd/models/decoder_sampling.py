@@ -7,7 +7,8 @@ early stopping the output is cut where every row has emitted EOS.  One dense dec
 host sync; `load_from_decoder` is an explicit extension to sample from trained weights, and `sample=True` the true categorical
 sampling the reference marks TODO (decoder_sampling.py:115-116): an extension with no reference behaviour to match.  So is
 `generate_beam` (beam search with scores, csrc/beam.hip); `decoder.sequence_log_prob` scores given sequences; and
-`sample=True` with `top_k` / `top_p` (truncated sampling, csrc/sample.hip); and `generate_map` / `token_marginals` /
+`sample=True` with `top_k` / `top_p` (truncated sampling, csrc/sample.hip) and with `min_p` / `typical_p` / `min_length`
+(min-p, locally typical and minimum-length sampling, same file); and `generate_map` / `token_marginals` /
 `length_distribution`: the exact most probable sequence and the exact per-step token and length distributions of the chain the
 dense table defines (csrc/chain.hip); and `generate_kbest`: the exact K most probable sequences of that chain (csrc/kbest.hip);
 and `length_penalty=` on both (the exact optimum of the length-normalised score), `best_by_length` (the best score of every
@@ -62,14 +63,27 @@ class MLXAutoregressiveDecoderSampling:
 
     def generate_with_temperature(self, z, conditions, max_length: int = 80, temperature: float = 1.0,
                                   early_stopping: bool = True, use_graph: bool = True, *, sample: bool = False,
-                                  seed: int = 0, top_k=None, top_p=None) -> torch.Tensor:
+                                  seed: int = 0, top_k=None, top_p=None, min_p=None, typical_p=None,
+                                  min_length: int = 0) -> torch.Tensor:
         """[B, t_stop] int32 tokens (models/decoder_sampling.py:48-128).  z is accepted and unused (Q2).
         sample=True (keyword-only extension; the default reproduces the reference's greedy "temperature sampling", Q9): every token is
         DRAWN from softmax(logits / temperature) -- what decoder_sampling.py:115-116 leaves as a TODO -- with a counter-based
         generator keyed by (seed, row, step): the same seed returns the same molecules.
         top_k / top_p (keyword-only extension, with sample=True): draw from the truncated distribution instead -- the top_k most
         likely tokens (ties to the lower token), then the smallest prefix of them holding top_p of their renormalised mass
-        (include/arcvae_hip.h arcvae_dec_sample_chain_topkp).  None = no truncation of that kind; both None = the categorical path."""
+        (include/arcvae_hip.h arcvae_dec_sample_chain_topkp).  None = no truncation of that kind; both None = the categorical path.
+        min_p / typical_p / min_length (keyword-only extension, with sample=True; include/arcvae_hip.h
+        arcvae_dec_sample_chain_trunc): min_p keeps the tokens whose probability is at least min_p times the row's largest (on top
+        of top_k / top_p; 0.0 = off); typical_p keeps the smallest prefix, holding typical_p of the top_k tokens' mass, of the
+        tokens ordered by |log p + H|, H the row's entropy (locally typical sampling; 1.0 = off; not together with top_p or
+        min_p); min_length > 0 masks the end token at the steps t < min_length, so no row ends before min_length tokens -- the
+        local mask of the usual minimum-length processor, NOT conditioning on the length: it changes the measure that is sampled.
+        None / 0 = off; with all three off the call runs exactly what it runs without them."""
+        if min_p is not None or typical_p is not None or min_length != 0:
+            if not sample:
+                raise ValueError("min_p / typical_p / min_length need sample=True")
+            return self._generate_trunc(conditions, max_length, temperature, early_stopping, use_graph, int(seed), top_k, top_p,
+                                        min_p, typical_p, min_length)
         if top_k is not None or top_p is not None:
             if not sample:
                 raise ValueError("top_k / top_p need sample=True")
@@ -118,17 +132,9 @@ class MLXAutoregressiveDecoderSampling:
         truncates every table row once, and a wave per row walks start token -> drawn token -> ... through those lists.  The seed is
         read by the kernel from a device word written before the launch, so the pass is captured once per (B, max_length,
         temperature, top_k, top_p) and replayed for every seed; use_graph=False launches the same kernels eagerly."""
-        check_temperature(temperature)
-        k = 0 if top_k is None else int(top_k)
-        if top_k is not None and k < 1:
-            raise ValueError("top_k must be >= 1")
-        p = 1.0 if top_p is None else float(top_p)
-        if not 0.0 < p <= 1.0 or not 0.0 < float(C.c_float(p).value) <= 1.0:
-            raise ValueError("top_p must lie in (0, 1]")
+        k, p = self._check_topkp(temperature, top_k, top_p)
         dec = self.decoder
         V = dec.vocab_size
-        if V > 256:
-            raise ValueError("top-k / top-p sampling needs vocab_size <= 256")
         ws, B = dec.load_conditions(conditions, max_length)
         st = self._state(("topkp", B, max_length, float(temperature), k, p), B, max_length,
                          lambda: dict(seed=torch.zeros(1, dtype=torch.int64, device=dec.store.device),
@@ -140,6 +146,56 @@ class MLXAutoregressiveDecoderSampling:
             dec.dense_table(ws)
             call("arcvae_dec_sample_chain_topkp", ptr(ws.logits), ptr(st["tokens"]), ptr(st["first_end"]), ptr(st["scratch"]),
                  st["scratch"].numel(), B, V, max_length, dec.end_token, float(temperature), k, p, ptr(st["seed"]), stream_ptr())
+
+        _launch(st, enqueue, use_graph)
+        return _stopped(st["tokens"], st["first_end"], early_stopping)
+
+    def _check_topkp(self, temperature, top_k, top_p):
+        """(k, p) as the kernels take them (0 / 1.0 = off), checked as the truncated walks need them."""
+        check_temperature(temperature)
+        k = 0 if top_k is None else int(top_k)
+        if top_k is not None and k < 1:
+            raise ValueError("top_k must be >= 1")
+        p = 1.0 if top_p is None else float(top_p)
+        if not 0.0 < p <= 1.0 or not 0.0 < float(C.c_float(p).value) <= 1.0:
+            raise ValueError("top_p must lie in (0, 1]")
+        if self.decoder.vocab_size > 256:
+            raise ValueError("top-k / top-p sampling needs vocab_size <= 256")
+        return k, p
+
+    def _generate_trunc(self, conditions, max_length: int, temperature: float, early_stopping: bool, use_graph: bool, seed: int,
+                        top_k, top_p, min_p, typical_p, min_length) -> torch.Tensor:
+        """As _generate_topkp with arcvae_dec_sample_chain_trunc as the walk: the pre-pass writes the lists by the min-p or the
+        typical rule, and with min_length > 0 a second set with the end token banned, which the steps t < min_length read.
+        Captured once per (B, max_length, temperature, top_k, top_p, min_p, typical_p, min_length), replayed for every seed."""
+        k, p = self._check_topkp(temperature, top_k, top_p)
+        mp = 0.0 if min_p is None else float(min_p)
+        if not 0.0 <= mp < 1.0 or not float(C.c_float(mp).value) < 1.0:
+            raise ValueError("min_p must lie in [0, 1)")
+        tp = 1.0 if typical_p is None else float(typical_p)
+        if not 0.0 < tp <= 1.0 or not 0.0 < float(C.c_float(tp).value) <= 1.0:
+            raise ValueError("typical_p must lie in (0, 1]")
+        mp, tp = float(C.c_float(mp).value), float(C.c_float(tp).value)      # as the kernel receives them
+        if tp < 1.0 and (p < 1.0 or mp > 0.0):
+            raise ValueError("typical_p does not combine with top_p or min_p")
+        dec = self.decoder
+        V, m = dec.vocab_size, int(min_length)
+        if not 0 <= m <= int(max_length):
+            raise ValueError("min_length must lie in [0, max_length]")
+        if m > 0 and (V < 2 or not 0 <= dec.end_token < V):
+            raise ValueError("min_length needs vocab_size >= 2 and 0 <= end_token < vocab_size")
+        ws, B = dec.load_conditions(conditions, max_length)
+        st = self._state(("trunc", B, max_length, float(temperature), k, p, mp, tp, m), B, max_length,
+                         lambda: dict(seed=torch.zeros(1, dtype=torch.int64, device=dec.store.device),
+                                      scratch=dec.scratch("trunc", B, V, k, m)))
+        s64 = seed & 0xFFFFFFFFFFFFFFFF
+        st["seed"].fill_(s64 - (1 << 64) if s64 >= 1 << 63 else s64)       # the 64-bit word the kernel reads
+
+        def enqueue():
+            dec.dense_table(ws)
+            call("arcvae_dec_sample_chain_trunc", ptr(ws.logits), ptr(st["tokens"]), ptr(st["first_end"]), ptr(st["scratch"]),
+                 st["scratch"].numel(), B, V, max_length, m, dec.end_token, float(temperature), k, p, mp, tp, ptr(st["seed"]),
+                 stream_ptr())
 
         _launch(st, enqueue, use_graph)
         return _stopped(st["tokens"], st["first_end"], early_stopping)

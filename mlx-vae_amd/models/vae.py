@@ -34,7 +34,8 @@ class ARCVAE:
     def generate(self, batch_size: int, conditions, max_length: int = 80, temperature: float = 1.0, *, sample: bool = False,
                  seed: int = 0, beam_width: Optional[int] = None, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, exact: bool = False, num_best: Optional[int] = None,
-                 length_penalty=None, num_samples: Optional[int] = None) -> torch.Tensor:
+                 length_penalty=None, num_samples: Optional[int] = None, min_p: Optional[float] = None,
+                 typical_p: Optional[float] = None, min_length: int = 0) -> torch.Tensor:
         """models/vae.py:101-131: z ~ N(0,I) (unused downstream, Q2) -> greedy sampler.  sample / seed (keyword-only extension):
         true categorical sampling instead of the reference's argmax, see MLXAutoregressiveDecoderSampling.  beam_width
         (keyword-only extension): the best hypothesis of a beam search of that width, [B, L] (generate_beam, early stopping).
@@ -45,14 +46,17 @@ class ARCVAE:
         length_penalty (keyword-only extension, with exact=True): the exact optimum (or K best) of log-probability / n ** alpha,
         or max_length divisors -- see generate_map; tokens only, as without it.  num_samples=K (keyword-only extension, with
         sample=True): K DISTINCT random sequences of every row, [B, K, L] -- a sample without replacement
-        (generate_without_replacement, seeded by `seed`); exclusive with beam_width, exact, top_k and top_p."""
+        (generate_without_replacement, seeded by `seed`); exclusive with beam_width, exact, top_k and top_p.  min_p / typical_p /
+        min_length (keyword-only extension, with sample=True): min-p and locally typical truncation and the minimum-length mask of
+        the end token, see generate_with_temperature; exclusive with beam_width, exact and num_samples."""
+        trunc = min_p is not None or typical_p is not None or min_length != 0
         dev = self.decoder_sampling.decoder.store.device
         z = torch.randn(batch_size, self.latent_dim, device=dev)
         if num_samples is not None:
             if not sample:
                 raise ValueError("num_samples needs sample=True")
-            if exact or beam_width is not None or top_k is not None or top_p is not None:
-                raise ValueError("num_samples is exclusive with beam_width, exact, top_k and top_p")
+            if exact or beam_width is not None or top_k is not None or top_p is not None or trunc:
+                raise ValueError("num_samples is exclusive with beam_width, exact, top_k, top_p, min_p, typical_p and min_length")
             return self.decoder_sampling.generate_without_replacement(z, conditions, max_length=max_length, num_samples=num_samples,
                                                                       temperature=temperature, seed=seed)[0]
         if num_best is not None and not exact:
@@ -60,8 +64,8 @@ class ARCVAE:
         if length_penalty is not None and not exact:
             raise ValueError("length_penalty needs exact=True")
         if exact:
-            if sample or beam_width is not None or top_k is not None or top_p is not None:
-                raise ValueError("exact=True is exclusive with sample, beam_width, top_k and top_p")
+            if sample or beam_width is not None or top_k is not None or top_p is not None or trunc:
+                raise ValueError("exact=True is exclusive with sample, beam_width, top_k, top_p, min_p, typical_p and min_length")
             if num_best is not None:
                 return self.decoder_sampling.generate_kbest(z, conditions, max_length=max_length, num_best=num_best,
                                                             temperature=temperature, length_penalty=length_penalty)[0]
@@ -70,8 +74,8 @@ class ARCVAE:
         if beam_width is not None:
             if sample:
                 raise ValueError("beam_width and sample=True are exclusive")
-            if top_k is not None or top_p is not None:
-                raise ValueError("top_k / top_p do not apply to beam search")
+            if top_k is not None or top_p is not None or trunc:
+                raise ValueError("top_k / top_p / min_p / typical_p / min_length do not apply to beam search")
             tokens, _ = self.decoder_sampling.generate_beam(z, conditions, max_length=max_length, beam_width=beam_width,
                                                             temperature=temperature)
             best = tokens[:, 0, :]
@@ -80,7 +84,8 @@ class ARCVAE:
             return best[:, :int(length.max().item())].contiguous()
         return self.decoder_sampling.generate_with_temperature(z, conditions, max_length=max_length,
                                                                temperature=temperature, sample=sample, seed=seed,
-                                                               top_k=top_k, top_p=top_p)
+                                                               top_k=top_k, top_p=top_p, min_p=min_p, typical_p=typical_p,
+                                                               min_length=min_length)
 
     def parameters(self):
         return {"encoder": self.encoder.parameters(), "decoder": self.decoder.parameters(),
