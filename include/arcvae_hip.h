@@ -573,6 +573,38 @@ int arcvae_dec_trunc_ws_bytes(int B, int V, int top_k, int min_len, long* bytes)
 int arcvae_dec_sample_chain_trunc(const float* dense_logits, int32_t* tokens, int32_t* first_end, void* ws, long ws_bytes, int B,
                                   int V, int max_len, int min_len, int end_token, float temperature, int top_k, float top_p,
                                   float min_p, float typical_p, const unsigned long long* seed, arcvae_stream_t stream);
+/* N independent draws per batch row from ONE dense table: the i.i.d. sampler behind "N molecules for this condition row".  The
+ * caller passes each distinct condition row once; the table and the lists are built once per row, whatever N is.
+ * Lists: the pre-pass is that of arcvae_dec_sample_chain_trunc, unchanged: it truncates the B*V table rows into one list set, or
+ *   two with min_len > 0, in the same workspace layout (arcvae_dec_sample_draws_ws_bytes = arcvae_dec_trunc_ws_bytes).  A list
+ *   set holds per table row the count n, the tokens as bytes and the fp32 cumulative masses C.  With every rule off (top_k = 0,
+ *   top_p = 1, min_p = 0, typical_p = 1) the lists hold the whole row: the categorical sampler in list arithmetic, bit-equal to
+ *   top_p = 1.0 of arcvae_dec_sample_chain_topkp and NOT to arcvae_dec_sample_chain_categorical, whose arithmetic differs.
+ * Draw keys, in 64-bit wrapping arithmetic: key(b, 0) = the row key of the common contract, mix64(seed ^ (b << 32));
+ *   key(b, d) = mix64(key(b, 0) ^ (0xD1B54A32D192ED03 * d)) for d >= 1.  A pure function of (seed, b, d): never of N, of the
+ *   launch shape or of which workgroup or lane runs the draw.
+ * Step t of a draw at token c (the start token 0 at t = 0) reads table row b*V + c, in the banned set while t < min_len:
+ *   u24 = mix64(key + t) >> 40, theta = fl(fl(u24 * 2^-24) * C_{n-1}) with n = min(max(count, 1), S), S the lists' row length; the
+ *   pick is the FIRST position i < n with C_i > theta, n - 1 if there is none; the next token is min(tok[pick], V - 1).  This is
+ *   the rule of arcvae_dec_sample_chain_topkp / _trunc, operation for operation.  (C need not be non-decreasing in fp32: the
+ *   scan's association order can step it down by an ulp at a multiple of 4.  "First position" is the rule; a bisection is not.)
+ * Outputs: tokens [B, N, max_len]; first_end [B, N] = the first step whose token is end_token, max_len without one.
+ *   pad_token = -1: the walk continues past the end, as the walks above.  0 <= pad_token <= 255: the positions after the first
+ *   end hold pad_token and the draw stops consuming steps; the tokens up to and including the first end and first_end are the
+ *   same in both modes.
+ * Consequences: draw 0 with pad_token = -1 IS arcvae_dec_sample_chain_trunc, bit for bit, for the same arguments and seed; the
+ *   draws of a call with N are the first N draws of a call with any larger N.
+ * Limits: the common contract's and those of arcvae_dec_sample_chain_trunc, plus N >= 1; B * N <= 2^31 - 1 (a draw's index is an
+ *   int), B * (N + 255) <= 2^32 - 1 (the walk's launch: B * ceil(N / w) workgroups of w <= 256 threads) and B * N * max_len <= 2^60
+ *   (output offsets are 64-bit); pad_token -1 or in [0, 255]; ws_bytes at least the query.
+ *   Anything else is ARCVAE_ERR_ARG before any launch.
+ * seed is a DEVICE word (one captured graph serves every seed).  Capture-safe, no atomics, no allocation; repeated calls are
+ *   bitwise identical. */
+int arcvae_dec_sample_draws_ws_bytes(int B, int V, int top_k, int min_len, long* bytes);
+int arcvae_dec_sample_draws(const float* dense_logits, int32_t* tokens /*[B,N,max_len]*/, int32_t* first_end /*[B,N]*/, void* ws,
+                            long ws_bytes, int B, int N, int V, int max_len, int min_len, int end_token,
+                            int pad_token /* -1: none */, float temperature, int top_k, float top_p, float min_p, float typical_p,
+                            const unsigned long long* seed, arcvae_stream_t stream);
 /* Sampling WITHOUT replacement: K distinct sequences per batch row that are exactly a sample without replacement from the sequence
  * distribution arcvae_dec_sample_chain_categorical draws from (stochastic beam search: Kool, van Hoof and Welling, ICML 2019).
  * ws: the back pointers.  arcvae_dec_swor, per batch row b:

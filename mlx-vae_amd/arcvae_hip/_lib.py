@@ -108,6 +108,8 @@ SIGNATURES = {
     "arcvae_dec_trunc_rows": [_vp, _l, _vp, _l, _i, _f, _i, _f, _f, _f, _i, _vp, _vp, _vp, _vp, _vp, _vp],
     "arcvae_dec_trunc_ws_bytes": [_i, _i, _i, _i, _lp],
     "arcvae_dec_sample_chain_trunc": [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp, _vp],
+    "arcvae_dec_sample_draws_ws_bytes": [_i, _i, _i, _i, _lp],
+    "arcvae_dec_sample_draws": [_vp, _vp, _vp, _vp, _l, _i, _i, _i, _i, _i, _i, _i, _f, _i, _f, _f, _f, _vp, _vp],
     "arcvae_dec_swor_ws_bytes": [_i, _i, _i, _lp],
     "arcvae_dec_swor": [_vp] * 9 + [_l, _i, _i, _i, _i, _i, _i, _f, _vp],
     "arcvae_dec_backward_dense": [_vp, _pp, _pp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp,

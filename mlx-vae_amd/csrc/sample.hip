@@ -379,6 +379,30 @@ int trunc_set_size(int V, int top_k, int ban) { return min(topkp_set_size(V, top
 // one list set, or two with min_len > 0 (the second with the end token banned), each of the top-k / top-p size
 long trunc_ws_bytes(int B, int V, int top_k, int min_len) { return (min_len > 0 ? 2 : 1) * topkp_ws_bytes(B, V, top_k); }
 
+// The pre-pass of the list walks (arcvae_dec_sample_chain_trunc, arcvae_dec_sample_draws): lays the list sets out in ws and
+// truncates all B*V table rows into them.  set[0]: the plain lists; set[1] (min_len > 0 only, otherwise = set[0]): the lists with
+// the end token banned.  The arrays of one kind lie together, count | cum | tok, so that every int32 and fp32 array stays 4-byte
+// aligned whatever R * S is
+void trunc_prepass(const float* dense_logits, void* ws, int B, int V, int min_len, int end_token, float temperature, int top_k,
+                   float top_p, float min_p, float typical_p, hipStream_t stream, TruncSet (&set)[2]) {
+    const long R = (long)B * V, S = topkp_set_size(V, top_k), sets = min_len > 0 ? 2 : 1;
+    for (long i = 0; i < sets; ++i) {
+        int32_t* count = (int32_t*)ws + i * R;
+        float* cum = (float*)((int32_t*)ws + sets * R) + i * R * S;
+        uint8_t* tok = (uint8_t*)((float*)((int32_t*)ws + sets * R) + sets * R * S) + i * R * S;
+        const int ban = i ? end_token : -1;
+        set[i] = {count, (void*)tok, cum, trunc_set_size(V, top_k, ban), ban};
+    }
+    if (sets == 1) set[1] = set[0];
+    const dim3 grid((unsigned)((R + 3) / 4), min_len > 0 ? 2 : 1);
+    if (typical_p < 1.f)
+        hipLaunchKernelGGL((trunc_rows_kernel<true, true>), grid, dim3(256), 0, stream, dense_logits, R, (const int32_t*)nullptr, R,
+                           V, 1.0f / temperature, (int)S, top_p, min_p, typical_p, set[0], set[1], (float*)nullptr, (float*)nullptr);
+    else
+        hipLaunchKernelGGL((trunc_rows_kernel<true, false>), grid, dim3(256), 0, stream, dense_logits, R, (const int32_t*)nullptr, R,
+                           V, 1.0f / temperature, (int)S, top_p, min_p, typical_p, set[0], set[1], (float*)nullptr, (float*)nullptr);
+}
+
 }  // namespace
 
 extern "C" int arcvae_dec_topkp_rows(const float* dense_logits, long table_rows, const int32_t* rows, long R, int V,
@@ -449,25 +473,9 @@ extern "C" int arcvae_dec_sample_chain_trunc(const float* dense_logits, int32_t*
         (min_len > 0 && (!table_end_ok(end_token, V) || V < 2)))
         return ARCVAE_ERR_ARG;
     if (ws_bytes < trunc_ws_bytes(B, V, top_k, min_len) || ((long)B * V + 3) / 4 > 0x7fffffffL) return ARCVAE_ERR_ARG;
-    const long R = (long)B * V, S = topkp_set_size(V, top_k), sets = min_len > 0 ? 2 : 1;
-    // list set 0: the plain lists; set 1 (min_len > 0 only): the lists with the end token banned.  The arrays of one kind lie
-    // together, count | cum | tok, so that every int32 and fp32 array stays 4-byte aligned whatever R * S is
+    const long S = topkp_set_size(V, top_k);
     TruncSet set[2];
-    for (long i = 0; i < sets; ++i) {
-        int32_t* count = (int32_t*)ws + i * R;
-        float* cum = (float*)((int32_t*)ws + sets * R) + i * R * S;
-        uint8_t* tok = (uint8_t*)((float*)((int32_t*)ws + sets * R) + sets * R * S) + i * R * S;
-        const int ban = i ? end_token : -1;
-        set[i] = {count, (void*)tok, cum, trunc_set_size(V, top_k, ban), ban};
-    }
-    if (sets == 1) set[1] = set[0];
-    const dim3 grid((unsigned)((R + 3) / 4), min_len > 0 ? 2 : 1);
-    if (typical_p < 1.f)
-        hipLaunchKernelGGL((trunc_rows_kernel<true, true>), grid, dim3(256), 0, stream, dense_logits, R, (const int32_t*)nullptr, R,
-                           V, 1.0f / temperature, (int)S, top_p, min_p, typical_p, set[0], set[1], (float*)nullptr, (float*)nullptr);
-    else
-        hipLaunchKernelGGL((trunc_rows_kernel<true, false>), grid, dim3(256), 0, stream, dense_logits, R, (const int32_t*)nullptr, R,
-                           V, 1.0f / temperature, (int)S, top_p, min_p, typical_p, set[0], set[1], (float*)nullptr, (float*)nullptr);
+    trunc_prepass(dense_logits, ws, B, V, min_len, end_token, temperature, top_k, top_p, min_p, typical_p, stream, set);
     if (min_len > 0) {
         const WalkMinLen ml = {set[1].count, set[1].cum, (const uint8_t*)set[1].tokens, min_len};
         hipLaunchKernelGGL(topkp_walk_kernel<WalkMinLen>, dim3(ceil_div(B, 4)), dim3(256), 0, stream, set[0].count, set[0].cum,
@@ -476,5 +484,188 @@ extern "C" int arcvae_dec_sample_chain_trunc(const float* dense_logits, int32_t*
         hipLaunchKernelGGL(topkp_walk_kernel<>, dim3(ceil_div(B, 4)), dim3(256), 0, stream, set[0].count, set[0].cum,
                            (const uint8_t*)set[0].tokens, tokens, first_end, B, V, (int)S, max_len, end_token, seed);
     }
+    return arcvae_launch_status();
+}
+
+// ---- N independent draws per batch row (arcvae_dec_sample_draws; restated by tests/draws_ref.py): the lists of the pre-pass above,
+// walked by ONE THREAD PER DRAW.  A workgroup takes one batch row b and blockDim.x consecutive draws; all its walkers read row b's
+// V lists, so it stages them in LDS once (per set: count [V] | cum [V, S] | the token bytes from the dword that holds the first
+// one) and a step costs LDS reads only.  STAGED = false is the same body reading the lists where the pre-pass left them (through
+// L2): what the launcher takes when the sets exceed the LDS cap -- V = 256 untruncated is 328 KB per set.
+// The pick is a front-to-back scan with early exit, four positions a round: C is NOT monotone in fp32 (the pre-pass forms a lane's
+// last element as fl(before + run) and the next lane's base in another association order, so C can step down by an ulp at a
+// multiple of 4), and the contract's pick is the FIRST position with C_i > theta -- the scan is that rule as written, a bisection
+// is not.  In the s-descending family the mass sits at the front: the expected number of reads is the expected rank of the token.
+// Workgroup size and LDS cap are read once per process (ARCVAE_DRAWS_WG = 64 | 128 | 256, ARCVAE_DRAWS_LDS_CAP in bytes, 0 = never
+// stage) so that tools/bench_draws.py can time the variants.  The defaults are what it measured on the WHOLE call, staging
+// included (profiles/draws_bench.json): see there for the figures.
+namespace {
+
+struct DrawLists {
+    const int32_t* count;
+    const float* cum;
+    const uint8_t* tok;
+};
+
+// key(b, 0) = the row key (draw 0 is the walk above); key(b, d) = mix64(row key ^ (0xD1B54A32D192ED03 * d)), 64-bit wrapping
+__device__ __forceinline__ unsigned long long draw_key(unsigned long long row_key, unsigned long long d) {
+    return d == 0 ? row_key : mix64(row_key ^ (0xD1B54A32D192ED03ull * d));
+}
+
+// dwords of one staged list set: V counts, V*S masses, and the V*S token bytes behind up to 3 bytes of lead (the source is copied
+// from the dword that holds its first byte)
+__host__ __device__ inline int draws_set_words(int V, int S) { return V + V * S + (V * S + 6) / 4; }
+
+// Copies batch row b's lists (table rows r0 .. r0 + V) of one set into dst; returns the lead: token byte i is byte lead + i of the
+// token words.  Whole dwords where the source holds them, single bytes at the tail: nothing is read outside the three arrays.
+__device__ __forceinline__ int draws_stage(const DrawLists g, long r0, int V, int S, uint32_t* dst) {
+    const int VS = V * S, tid = threadIdx.x, nt = blockDim.x;
+    const int32_t* cnt = g.count + r0;
+    for (int i = tid; i < V; i += nt) dst[i] = (uint32_t)cnt[i];
+    const float* cm = g.cum + r0 * S;
+    for (int i = tid; i < VS; i += nt) dst[V + i] = __float_as_uint(cm[i]);
+    const uint8_t* tk = g.tok + r0 * S;
+    const int lead = (int)((unsigned long long)tk & 3ull);
+    const uint8_t* tk_al = tk - lead;                     // (lead > 0: the bytes before tk are the arrays before it in ws)
+    const int total = lead + VS, full = total >> 2;
+    uint32_t* d32 = dst + V + VS;
+    for (int i = tid; i < full; i += nt) d32[i] = ((const uint32_t*)tk_al)[i];
+    for (int i = 4 * full + tid; i < total; i += nt) ((uint8_t*)d32)[i] = tk_al[i];
+    return lead;
+}
+
+// The contract's pick on one list: the first position i < n with C_i > theta, n - 1 if there is none; cum(i) loads C_i (from LDS
+// or through L2).  Front to back, four positions a round, out at the first round that holds one.
+template <class Load>
+__device__ __forceinline__ int draws_pick(int n, float theta, Load cum) {
+    for (int i0 = 0; i0 < n; i0 += 4) {
+        float c[4];
+#pragma unroll
+        for (int e = 0; e < 4; ++e) c[e] = i0 + e < n ? cum(i0 + e) : 0.f;
+        int hit = -1;
+#pragma unroll
+        for (int e = 3; e >= 0; --e)
+            if (i0 + e < n && c[e] > theta) hit = i0 + e;
+        if (hit >= 0) return hit;
+    }
+    return n - 1;
+}
+
+template <bool STAGED, bool MINLEN>
+__global__ __launch_bounds__(256) void draws_walk_kernel(DrawLists plain, DrawLists banned, int32_t* __restrict__ tokens,
+                                                         int32_t* __restrict__ first_end, int N, int V, int S, int max_len,
+                                                         int min_len, int end_token, int pad_token, int chunks,
+                                                         const unsigned long long* __restrict__ seed_ptr) {
+    extern __shared__ __attribute__((aligned(16))) uint32_t draws_lds[];
+    const int b = blockIdx.x / chunks;
+    const long d = (long)(blockIdx.x - b * chunks) * blockDim.x + threadIdx.x;
+    const long r0 = (long)b * V;
+    const int words = draws_set_words(V, S);
+    int lead0 = 0, lead1 = 0;
+    if (STAGED) {
+        lead0 = draws_stage(plain, r0, V, S, draws_lds);
+        if (MINLEN) lead1 = draws_stage(banned, r0, V, S, draws_lds + words);
+        __syncthreads();
+    }
+    const bool active = d < N;
+    if (!__any(active)) return;                           // wave-uniform (no barrier follows)
+    const unsigned long long key0 = draw_key(table_row_key(*seed_ptr, b), (unsigned long long)d);
+    int32_t* out = tokens + ((long)b * N + d) * max_len;  // (dereferenced by active threads only)
+    const bool pad = pad_token >= 0;
+    bool live = active;
+    int cur = 0, fe = max_len, t = 0;
+    for (; t < max_len; ++t) {
+        if (pad && !__any(live)) break;                   // every draw of the wave has ended: the rest is padding
+        if (live) {
+            const bool ban = MINLEN && t < min_len;
+            const unsigned long long rnd = mix64(key0 + (unsigned long long)t);
+            int n, pick;
+            float theta;
+            if (STAGED) {
+                const uint32_t* set = draws_lds + (ban ? words : 0);
+                const uint32_t* cm = set + V + cur * S;
+                n = min(max((int)set[cur], 1), S);
+                theta = (float)table_u24(rnd) * (1.0f / 16777216.0f) * __uint_as_float(cm[n - 1]);
+                pick = draws_pick(n, theta, [&](int i) { return __uint_as_float(cm[i]); });
+                cur = ((const uint8_t*)(set + V + V * S))[(ban ? lead1 : lead0) + cur * S + pick];
+            } else {
+                const DrawLists g = ban ? banned : plain;
+                const long r = r0 + cur;
+                const float* __restrict__ cm = g.cum + r * S;
+                n = min(max(g.count[r], 1), S);
+                theta = (float)table_u24(rnd) * (1.0f / 16777216.0f) * cm[n - 1];
+                pick = draws_pick(n, theta, [&](int i) { return cm[i]; });
+                cur = g.tok[r * S + pick];
+            }
+            cur = min(cur, V - 1);
+            out[t] = cur;
+            if (cur == end_token && fe == max_len) {
+                fe = t;
+                live = !pad;                              // with a pad token the draw stops consuming steps
+            }
+        } else if (active) {
+            out[t] = pad_token;
+        }
+    }
+    if (active) {
+        for (; t < max_len; ++t) out[t] = pad_token;      // (only after the early exit above)
+        first_end[(long)b * N + d] = fe;
+    }
+}
+
+int draws_wg() {
+    static const int v = arcvae_env_int("ARCVAE_DRAWS_WG", 128);
+    return v == 256 ? 256 : (v == 64 ? 64 : 128);
+}
+
+// the largest staged image, both sets together: 64 KB is what a workgroup gets without asking the runtime for more, and two
+// sets of the V = S = 80 workload (64 648 bytes) still fit
+long draws_lds_cap() {
+    static const int v = arcvae_env_int("ARCVAE_DRAWS_LDS_CAP", 64 * 1024);
+    return v < 0 ? 0 : (v > 64 * 1024 ? 64 * 1024 : v);
+}
+
+template <bool STAGED, bool MINLEN>
+void draws_launch(unsigned blocks, int wg, size_t lds, const DrawLists& plain, const DrawLists& banned, int32_t* tokens,
+                  int32_t* first_end, int N, int V, int S, int max_len, int min_len, int end_token, int pad_token, int chunks,
+                  const unsigned long long* seed, hipStream_t stream) {
+    hipLaunchKernelGGL((draws_walk_kernel<STAGED, MINLEN>), dim3(blocks), dim3(wg), lds, stream, plain, banned, tokens, first_end, N,
+                       V, S, max_len, min_len, end_token, pad_token, chunks, seed);
+}
+
+}  // namespace
+
+extern "C" int arcvae_dec_sample_draws_ws_bytes(int B, int V, int top_k, int min_len, long* bytes) {
+    return arcvae_dec_trunc_ws_bytes(B, V, top_k, min_len, bytes);
+}
+
+extern "C" int arcvae_dec_sample_draws(const float* dense_logits, int32_t* tokens, int32_t* first_end, void* ws, long ws_bytes, int B,
+                                       int N, int V, int max_len, int min_len, int end_token, int pad_token, float temperature,
+                                       int top_k, float top_p, float min_p, float typical_p, const unsigned long long* seed,
+                                       hipStream_t stream) {
+    if (!dense_logits || !tokens || !first_end || !ws || !seed || B <= 0 || N <= 0 || max_len <= 0 ||
+        !trunc_args_ok(V, temperature, top_k, top_p, min_p, typical_p) || !table_min_len_ok(min_len, max_len) ||
+        (min_len > 0 && (!table_end_ok(end_token, V) || V < 2)) || !(pad_token == -1 || table_pad_ok(pad_token)))
+        return ARCVAE_ERR_ARG;
+    if (ws_bytes < trunc_ws_bytes(B, V, top_k, min_len) || ((long)B * V + 3) / 4 > 0x7fffffffL) return ARCVAE_ERR_ARG;
+    if ((long)B * N > 0x7fffffffL || (long)B * N * max_len > (1L << 60)) return ARCVAE_ERR_ARG;   // draw and output indices
+    if ((long)B * ((long)N + 255) > 0xffffffffL) return ARCVAE_ERR_ARG;       // the launch: B * ceil(N / w) workgroups of w <= 256 threads
+    const int S = topkp_set_size(V, top_k);
+    TruncSet set[2];
+    trunc_prepass(dense_logits, ws, B, V, min_len, end_token, temperature, top_k, top_p, min_p, typical_p, stream, set);
+    const DrawLists plain = {set[0].count, set[0].cum, (const uint8_t*)set[0].tokens};
+    const DrawLists banned = {set[1].count, set[1].cum, (const uint8_t*)set[1].tokens};
+    const int wg = draws_wg(), chunks = (int)(((long)N + wg - 1) / wg);
+    const unsigned blocks = (unsigned)((long)B * chunks);
+    const long lds = (long)(min_len > 0 ? 2 : 1) * draws_set_words(V, S) * 4;
+    const bool staged = lds <= draws_lds_cap();
+#define DRAWS_LAUNCH(ST, ML)                                                                                                     \
+    draws_launch<ST, ML>(blocks, wg, ST ? (size_t)lds : 0, plain, banned, tokens, first_end, N, V, S, max_len, min_len, end_token, \
+                         pad_token, chunks, seed, stream)
+    if (staged && min_len > 0) DRAWS_LAUNCH(true, true);
+    else if (staged) DRAWS_LAUNCH(true, false);
+    else if (min_len > 0) DRAWS_LAUNCH(false, true);
+    else DRAWS_LAUNCH(false, false);
+#undef DRAWS_LAUNCH
     return arcvae_launch_status();
 }

@@ -16,7 +16,8 @@ length) and `generate_of_length` (the most probable sequence of a given length);
 random sequences per row, exactly a sample without replacement, with `importance_weights` for unbiased estimates (csrc/swor.hip);
 and `sequence_entropy` / `sequence_divergence` / `expected_token_counts` / `expected_length`: the exact entropy, cross-entropy
 and KL of the distribution over whole sequences and its expected token counts and length, closed forms on the forward recursion
-(csrc/table.hip row costs, csrc/chain.hip expectations; `_expect` is their one path).
+(csrc/table.hip row costs, csrc/chain.hip expectations; `_expect` is their one path); and `generate_many`: N independent draws
+per condition row from one dense table, the i.i.d. sampler of the list walk's measure (csrc/sample.hip, one thread per draw).
 
 Every method is its argument checks, the decoder's one path to the table -- `load_conditions`, `dense_table`, `table_lse`,
 `scratch` (models/decoder.py) -- and its own kernel.  What the methods share beyond that is written once below: `_state` +
@@ -168,22 +169,9 @@ class MLXAutoregressiveDecoderSampling:
         """As _generate_topkp with arcvae_dec_sample_chain_trunc as the walk: the pre-pass writes the lists by the min-p or the
         typical rule, and with min_length > 0 a second set with the end token banned, which the steps t < min_length read.
         Captured once per (B, max_length, temperature, top_k, top_p, min_p, typical_p, min_length), replayed for every seed."""
-        k, p = self._check_topkp(temperature, top_k, top_p)
-        mp = 0.0 if min_p is None else float(min_p)
-        if not 0.0 <= mp < 1.0 or not float(C.c_float(mp).value) < 1.0:
-            raise ValueError("min_p must lie in [0, 1)")
-        tp = 1.0 if typical_p is None else float(typical_p)
-        if not 0.0 < tp <= 1.0 or not 0.0 < float(C.c_float(tp).value) <= 1.0:
-            raise ValueError("typical_p must lie in (0, 1]")
-        mp, tp = float(C.c_float(mp).value), float(C.c_float(tp).value)      # as the kernel receives them
-        if tp < 1.0 and (p < 1.0 or mp > 0.0):
-            raise ValueError("typical_p does not combine with top_p or min_p")
+        k, p, mp, tp, m = self._check_trunc(temperature, top_k, top_p, min_p, typical_p, min_length, max_length)
         dec = self.decoder
-        V, m = dec.vocab_size, int(min_length)
-        if not 0 <= m <= int(max_length):
-            raise ValueError("min_length must lie in [0, max_length]")
-        if m > 0 and (V < 2 or not 0 <= dec.end_token < V):
-            raise ValueError("min_length needs vocab_size >= 2 and 0 <= end_token < vocab_size")
+        V = dec.vocab_size
         ws, B = dec.load_conditions(conditions, max_length)
         st = self._state(("trunc", B, max_length, float(temperature), k, p, mp, tp, m), B, max_length,
                          lambda: dict(seed=torch.zeros(1, dtype=torch.int64, device=dec.store.device),
@@ -199,6 +187,73 @@ class MLXAutoregressiveDecoderSampling:
 
         _launch(st, enqueue, use_graph)
         return _stopped(st["tokens"], st["first_end"], early_stopping)
+
+    def _check_trunc(self, temperature, top_k, top_p, min_p, typical_p, min_length, max_length):
+        """(k, p, min_p, typical_p, min_length) as the list walks take them (0 / 1.0 / 0.0 / 1.0 / 0 = off), checked as
+        arcvae_dec_sample_chain_trunc and arcvae_dec_sample_draws need them."""
+        k, p = self._check_topkp(temperature, top_k, top_p)
+        mp = 0.0 if min_p is None else float(min_p)
+        if not 0.0 <= mp < 1.0 or not float(C.c_float(mp).value) < 1.0:
+            raise ValueError("min_p must lie in [0, 1)")
+        tp = 1.0 if typical_p is None else float(typical_p)
+        if not 0.0 < tp <= 1.0 or not 0.0 < float(C.c_float(tp).value) <= 1.0:
+            raise ValueError("typical_p must lie in (0, 1]")
+        mp, tp = float(C.c_float(mp).value), float(C.c_float(tp).value)      # as the kernel receives them
+        if tp < 1.0 and (p < 1.0 or mp > 0.0):
+            raise ValueError("typical_p does not combine with top_p or min_p")
+        V, m = self.decoder.vocab_size, int(min_length)
+        if not 0 <= m <= int(max_length):
+            raise ValueError("min_length must lie in [0, max_length]")
+        if m > 0 and (V < 2 or not 0 <= self.decoder.end_token < V):
+            raise ValueError("min_length needs vocab_size >= 2 and 0 <= end_token < vocab_size")
+        return k, p, mp, tp, m
+
+    def generate_many(self, conditions, num_draws: int, max_length: int = 80, temperature: float = 1.0, *, seed: int = 0,
+                      top_k=None, top_p=None, min_p=None, typical_p=None, min_length: int = 0, early_stopping: bool = True,
+                      use_graph: bool = True):
+        """Extension (absent in the reference): num_draws INDEPENDENT random sequences per condition row -> (tokens [B, N, L]
+        int32, lengths [B, N] int32).  The draws of a row are i.i.d. from exactly the measure the list walk of
+        generate_with_temperature(sample=True, top_k / top_p / min_p / typical_p / min_length) samples -- with every rule off, the
+        model's own distribution at this temperature -- and draw 0 is that call's molecule for the same seed.  Sampling WITH
+        replacement: the same molecule may come twice; generate_without_replacement (num_samples) is the sampler of DISTINCT
+        molecules, at most 32 per row and from another measure once truncation is wanted.
+        For "N molecules at this property target" pass ONE condition row and num_draws = N, not N repeated rows: the dense table
+        and its truncation are computed once per row of `conditions`, whatever num_draws is, and only the walk grows with it
+        (include/arcvae_hip.h arcvae_dec_sample_draws: one thread per draw over the row's lists held in LDS).
+        Tokens after a draw's first end_token are pad_token; lengths = the first end_token's index + 1, max_length without one.
+        early_stopping: L = the longest draw; otherwise L = max_length.  The noise is keyed by (seed, row, draw, step): the same
+        seed returns the same molecules, and the draws of a call are the first num_draws draws of any larger call.  The seed is
+        read by the kernel from a device word, so the pass (dense table, pre-pass, walk) is captured once per (B, num_draws,
+        max_length, temperature, top_k, top_p, min_p, typical_p, min_length) and replayed for every seed; use_graph=False launches
+        the same kernels eagerly."""
+        k, p, mp, tp, m = self._check_trunc(temperature, top_k, top_p, min_p, typical_p, min_length, max_length)
+        N, T = int(num_draws), int(max_length)
+        if N < 1:
+            raise ValueError("num_draws must be >= 1")
+        if not 0 <= self.pad_token <= 255:
+            raise ValueError("needs 0 <= pad_token <= 255")
+        dec = self.decoder
+        V, dev = dec.vocab_size, dec.store.device
+        ws, B = dec.load_conditions(conditions, T)
+        if B * N > 2 ** 31 - 1 or B * (N + 255) > 2 ** 32 - 1:
+            raise ValueError("need rows * num_draws <= 2**31 - 1 and rows * (num_draws + 255) <= 2**32 - 1")
+
+        # the walk's buffers under _state's own names: tokens [B * N, T] and first_end [B * N] are [B, N, T] and [B, N] in memory
+        st = self._state(("draws", B, N, T, float(temperature), k, p, mp, tp, m), B * N, T,
+                         lambda: dict(seed=torch.zeros(1, dtype=torch.int64, device=dev),
+                                      scratch=dec.scratch("sample_draws", B, V, k, m)))
+        s64 = int(seed) & 0xFFFFFFFFFFFFFFFF
+        st["seed"].fill_(s64 - (1 << 64) if s64 >= 1 << 63 else s64)       # the 64-bit word the kernel reads
+
+        def enqueue():
+            dec.dense_table(ws)
+            call("arcvae_dec_sample_draws", ptr(ws.logits), ptr(st["tokens"]), ptr(st["first_end"]), ptr(st["scratch"]),
+                 st["scratch"].numel(), B, N, V, T, m, dec.end_token, self.pad_token, float(temperature), k, p, mp, tp,
+                 ptr(st["seed"]), stream_ptr())
+
+        _launch(st, enqueue, use_graph)
+        tokens, lengths = st["tokens"].view(B, N, T), torch.clamp(st["first_end"].view(B, N) + 1, max=T)
+        return (_cut(tokens, lengths) if early_stopping else tokens).clone(), lengths
 
     def _check_lengths(self, max_length, min_length):
         """(max_length, min_length) as ints, checked as generate_beam, generate_map and generate_kbest need them."""

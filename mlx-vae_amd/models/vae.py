@@ -35,7 +35,7 @@ class ARCVAE:
                  seed: int = 0, beam_width: Optional[int] = None, top_k: Optional[int] = None,
                  top_p: Optional[float] = None, exact: bool = False, num_best: Optional[int] = None,
                  length_penalty=None, num_samples: Optional[int] = None, min_p: Optional[float] = None,
-                 typical_p: Optional[float] = None, min_length: int = 0) -> torch.Tensor:
+                 typical_p: Optional[float] = None, min_length: int = 0, num_draws: Optional[int] = None) -> torch.Tensor:
         """models/vae.py:101-131: z ~ N(0,I) (unused downstream, Q2) -> greedy sampler.  sample / seed (keyword-only extension):
         true categorical sampling instead of the reference's argmax, see MLXAutoregressiveDecoderSampling.  beam_width
         (keyword-only extension): the best hypothesis of a beam search of that width, [B, L] (generate_beam, early stopping).
@@ -48,8 +48,21 @@ class ARCVAE:
         sample=True): K DISTINCT random sequences of every row, [B, K, L] -- a sample without replacement
         (generate_without_replacement, seeded by `seed`); exclusive with beam_width, exact, top_k and top_p.  min_p / typical_p /
         min_length (keyword-only extension, with sample=True): min-p and locally typical truncation and the minimum-length mask of
-        the end token, see generate_with_temperature; exclusive with beam_width, exact and num_samples."""
+        the end token, see generate_with_temperature; exclusive with beam_width, exact and num_samples.  num_draws=N (keyword-only
+        extension, with sample=True): N INDEPENDENT random sequences of every condition row, [B, N, L], pad_token after each one's
+        end (generate_many, seeded by `seed`) -- i.i.d. draws from the measure the list walk samples, combined with top_k, top_p,
+        min_p, typical_p and min_length as there; exclusive with beam_width, exact, num_best, num_samples (the sampler WITHOUT
+        replacement) and length_penalty.  For N molecules at one property target pass ONE condition row and num_draws=N, not N
+        repeated rows: the table is then computed once.  The rows are those of `conditions`; batch_size is not used on this path."""
         trunc = min_p is not None or typical_p is not None or min_length != 0
+        if num_draws is not None:
+            if not sample:
+                raise ValueError("num_draws needs sample=True")
+            if exact or beam_width is not None or num_best is not None or num_samples is not None or length_penalty is not None:
+                raise ValueError("num_draws is exclusive with beam_width, exact, num_best, num_samples and length_penalty")
+            return self.decoder_sampling.generate_many(conditions, num_draws, max_length=max_length, temperature=temperature,
+                                                       seed=seed, top_k=top_k, top_p=top_p, min_p=min_p, typical_p=typical_p,
+                                                       min_length=min_length)[0]
         dev = self.decoder_sampling.decoder.store.device
         z = torch.randn(batch_size, self.latent_dim, device=dev)
         if num_samples is not None:
